@@ -7,7 +7,11 @@ hipGraph step replayed N times) -> spec_back -> iSTFT.  Workload = BASELINE.json
 full 65.6 M-parameter NCSN++, fp32, random-init weights).  N > 1: one process per GPU (torch.distributed, RCCL), every
 rank enhances its own batch (weak scaling), the only collective is one weight broadcast before the timed region.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the headline (metric, value,
+unit, higher_is_better, dtype, ms_per_step, config).  --dump-outputs DIR writes what the last timed step returned (the
+enhanced waveforms, float32, and its NFE count) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for
+output.  --full adds the extra objects (each can still be left out with its --no-* flag):
+  power        socket power and shader clock sampled during the timed region
   roofline     dominant kernel = the 3x3 convolution of the wide U-Net levels.  By default that is conv3x3_wino_kernel
                (kernels_conv_wino.h): 1-D Winograd F(2,3) along the frame axis on top of the fp16x2 operand split (fp32
                operands as two fp16 terms, three partial products on the f16 MFMA pipe, fp32 accumulate).  achieved =
@@ -74,6 +78,10 @@ def parse():
     ap.add_argument("--N", type=int, default=None)
     ap.add_argument("--snr", type=float, default=None)
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: power, roofline / per-class profile, cpu_baseline, other_workloads, parity")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-others", action="store_true", help="headline only: skip the configs[2] / configs[3] / batch-1 measurements attached as other_workloads")
@@ -81,7 +89,33 @@ def parse():
     ap.add_argument("--test-emulator", type=str, default=None, metavar="LIB",
                     help="TEST ONLY (tests/test_host_api.py): run the launcher / collective / reporting logic of this script on CPU "
                          "tensors with the workgroup-emulator build of the kernels and gloo, reduced-width network; never a measurement")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+DUMP_LIMIT_BYTES = 60 * 10**6          # (under the 64 MB cap with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays, rank, world):
+    """Writes {name: array} as out_dir/<name>.npy (float64 stays float64, everything else becomes float32); rank r > 0 adds a
+    _rank<r> suffix.  Each rank keeps to its share of DUMP_LIMIT_BYTES: an array that does not fit is replaced by a fixed, seeded
+    sample of its flattened elements (the same indices for the same shape in every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // world
+    conv = {}
+    for name, v in arrays.items():
+        arr = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+        conv[name] = arr.astype(np.float64 if arr.dtype == np.float64 else np.float32)
+    for name, arr in sorted(conv.items(), key=lambda kv: kv[1].nbytes):        # the small ones first: the largest takes the rest
+        if arr.nbytes > budget:
+            keep = budget // arr.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(arr.size, size=keep, replace=False))
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, (name if rank == 0 else f"{name}_rank{rank}") + ".npy"), arr)
+        budget -= arr.nbytes
 
 
 class PowerSampler:
@@ -371,8 +405,9 @@ class Env:
         self.sync()
 
 
-def measure(env, a, workload, batch, steps, warmup, sampler=None, N=None, snr=None, seconds=4.0, want_power=False):
-    """W untimed + K timed steps of one workload on every rank of `env`; returns (JSON object on rank 0 / None elsewhere, model)."""
+def measure(env, a, workload, batch, steps, warmup, sampler=None, N=None, snr=None, seconds=4.0, want_power=False, profile=False):
+    """W untimed + K timed steps of one workload on every rank of `env`; returns (JSON object on rank 0 / None elsewhere, model,
+    {name: output of the last timed step}).  `profile`: one instrumented evaluation after the timed region (roofline objects)."""
     torch, dist = env.torch, env.dist
     from sgmse_amd.model import ScoreModel
     from sgmse_amd.parallel import broadcast_backbone_weights
@@ -429,8 +464,9 @@ def measure(env, a, workload, batch, steps, warmup, sampler=None, N=None, snr=No
         per_rank = [float(t.item()) for t in every]
         elapsed = max(per_rank)                               # the job is done when its slowest rank is
     assert torch.isfinite(x_hat).all()
+    last = {"x_hat": x_hat, "nfe": torch.tensor(float(nfe), dtype=torch.float64)}
     if rank != 0:
-        return None, model
+        return None, model, last
 
     ctx = model.dnn.engine(dev)
     utts = world * batch * steps
@@ -474,7 +510,7 @@ def measure(env, a, workload, batch, steps, warmup, sampler=None, N=None, snr=No
                                      "note": "the only collective: one weight broadcast before the timed region"}
     if emu:
         out["data"] = "TEST ONLY: CPU workgroup emulator, reduced-width network -- not a measurement"
-    if not a.no_profile and not emu:
+    if profile and not emu:
         Y = torch.randn(batch, 2, wl["F"], T, dtype=torch.complex64, device=dev) * 0.3
         tt = torch.full((batch,), 0.5, device=dev)
         prof, _ = ctx.profile_forward(Y, tt)
@@ -501,7 +537,7 @@ def measure(env, a, workload, batch, steps, warmup, sampler=None, N=None, snr=No
             classes[k] = {"ms": round(v["ms"], 3), "launches": v["launches"],
                           ("tflops" if v["unit"] == "flop" else "gbps"): rate / (1e12 if v["unit"] == "flop" else 1e9)}
         out["kernel_classes_one_eval"] = classes
-    return out, model
+    return out, model, last
 
 
 def main():
@@ -514,11 +550,15 @@ def main():
     env = Env(a)
     if os.environ.get("SGMSE_PMC_CALIB") and env.rank == 0 and not env.emu:
         pmc_calibration_launches(env.dev)
-    out, model = measure(env, a, a.workload, a.batch, a.steps, a.warmup, sampler=a.sampler, N=a.N, snr=a.snr, seconds=a.seconds, want_power=True)
+    out, model, last = measure(env, a, a.workload, a.batch, a.steps, a.warmup, sampler=a.sampler, N=a.N, snr=a.snr, seconds=a.seconds,
+                               want_power=a.full, profile=a.full and not a.no_profile)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last, env.rank, env.world)
+    del last
     headline = (a.workload == "pc16k" and a.batch == 32 and a.sampler in (None, "pc") and a.N in (None, 30) and a.seconds == 4.0)
-    if env.rank == 0 and not a.no_cpu_baseline and env.world == 1 and a.workload == "pc16k" and not env.emu:
+    if a.full and env.rank == 0 and not a.no_cpu_baseline and env.world == 1 and a.workload == "pc16k" and not env.emu:
         out["cpu_baseline"] = cpu_baseline(model.dnn.state_dict(), a.cpu_evals, a.N or wl["N"], a.snr if a.snr is not None else wl["snr"])
-    if env.world == 1 and headline and not a.no_others and not env.emu:
+    if a.full and env.world == 1 and headline and not a.no_others and not env.emu:
         # The other BASELINE.json configurations one GPU holds, and the per-file (batch 1) latency of the drop-in path, in the same
         # line, each with its own roofline object: 1 warm-up + 1 (batch 1: 3) timed steps after the headline's timed region.
         del model
@@ -534,7 +574,7 @@ def main():
             saved = {k: os.environ.get(k) for k in envs}
             os.environ.update(envs)                       # (the engine re-reads its switches when a model is built)
             try:
-                o, m = measure(env, a, wname, batch, steps, 1)
+                o, m, _ = measure(env, a, wname, batch, steps, 1, profile=not a.no_profile)
                 del m
                 others[key] = {k: o[k] for k in ("metric", "value", "unit", "ms_per_step", "rtf", "steps", "warmup", "dtype", "config", "roofline",
                                                  "kernel_classes_one_eval", "graph_captures_rank0") if k in o}

@@ -847,9 +847,9 @@ def check_reference_script_unmodified(dev, tmp_path, monkeypatch):
     from sgmse_amd import enhancement as E
     from sgmse_amd.model import ScoreModel
     from sgmse_amd.data_module import SpecsDataModule
-    ref = os.path.join(os.environ.get("SGMSE_REFERENCE_DIR", "/root/reference"), "enhancement.py")
+    ref = os.path.join(ROOT, "oracle", "_ref", "enhancement.py")        # copied there by build() (oracle/build_ref.py)
     if not os.path.exists(ref):
-        pytest.skip("reference tree not present on this machine")
+        pytest.skip("oracle/_ref/enhancement.py missing: build() found no upstream tree to copy it from")
     hp = dict(backbone="ncsnpp", sde="ouve", nf=32, theta=1.5, sigma_min=0.05, sigma_max=0.5, N=30, t_eps=0.03,
               data_module_cls=SpecsDataModule, n_fft=510, hop_length=128, spec_factor=0.15, spec_abs_exponent=0.5)
     src = ScoreModel(**hp)

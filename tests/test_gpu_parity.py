@@ -37,7 +37,7 @@ def test_conv_kernel_variants(hip, variant):
     assert "VARIANT-OK" in out.stdout, out.stdout + out.stderr
 
 
-def test_conv_mfma_fused_groupnorm_statistics_path(hip):
+def test_conv_mfma_fused_groupnorm_statistics_path(hip, tmp_path):
     """Network-level check of the epilogue-fused GroupNorm statistics against the stand-alone statistics pass: the two
     engines must agree to rounding (same network, SGMSE_FUSE_GN_STATS toggled in a child process)."""
     import os, subprocess, sys
@@ -49,7 +49,7 @@ def test_conv_mfma_fused_groupnorm_statistics_path(hip):
             "torch.save(out.cpu(), sys.argv[1])\n") % (ROOT, os.path.join(ROOT, "tests"))
     outs = []
     for flag in ("1", "0"):
-        path = os.path.join("/tmp", f"gnfuse_{flag}.pt")
+        path = str(tmp_path / f"gnfuse_{flag}.pt")
         subprocess.run([sys.executable, "-c", code, path], check=True, env=dict(os.environ, SGMSE_FUSE_GN_STATS=flag), timeout=600)
         outs.append(torch.load(path))
     assert rel_l2(outs[0], outs[1]) < 2e-6

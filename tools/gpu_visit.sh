@@ -7,8 +7,8 @@
 #   micro      tools/conv_microbench.py (VARIANTS / SHAPES / FUSED / ROUNDS as that script reads them)
 #   trace      phase time stamps of a traced kernel instantiation (TRACE_VARIANTS, TRACE_SHAPE) through tools/analyze_trace.py
 #   power      tools/power_probe.py (CASES, ITERS)
-#   ab         bench.py A/B: AB = ';'-separated "name|bench args|ENV=1 ENV2=0" entries
-#   bench      bench.py with the driver's defaults -> ${TAG}_bench_b32.json
+#   ab         bench.py --full A/B: AB = ';'-separated "name|bench args|ENV=1 ENV2=0" entries
+#   bench      bench.py --full (defaults otherwise) -> ${TAG}_bench_b32.json
 #   rocprof    rocprofv3 --kernel-trace --stats of the bench command -> ${TAG}_bench_b32_kernel_stats.csv
 #   pmc        PMC passes of the dominant kernel's micro-benchmark (tools/conv_microbench.py) -> ${TAG}_pmc_*.json, ${TAG}_hbm_traffic_*.json
 #   pmcbench   PMC passes over the bench command itself at batch 32 (counters of the run's own launches of the dominant kernel)
@@ -71,15 +71,15 @@ if has ab; then
   IFS=';' read -ra ENTRIES <<< "$AB"
   for ent in "${ENTRIES[@]}"; do
     IFS='|' read -r name args envs <<< "$ent"
-    env $envs timeout 400 python bench.py $args > $O/ab_$name.json 2>$O/ab_$name.err
+    env $envs timeout 400 python bench.py --full $args > $O/ab_$name.json 2>$O/ab_$name.err
     val $O/ab_$name.json "$name [$envs] [$args]" | tee -a $O/${TAG}_ab.txt
   done
 fi
-if has bench; then echo "== bench (driver defaults)"; timeout 900 python bench.py > $O/${TAG}_bench_b32.json 2>$O/${TAG}_bench.err; echo "bench rc=$?"; cut -c1-900 $O/${TAG}_bench_b32.json; tail -2 $O/${TAG}_bench.err; fi
+if has bench; then echo "== bench --full"; timeout 900 python bench.py --full > $O/${TAG}_bench_b32.json 2>$O/${TAG}_bench.err; echo "bench rc=$?"; cut -c1-900 $O/${TAG}_bench_b32.json; tail -2 $O/${TAG}_bench.err; fi
 if has rocprof; then
   echo "== rocprofv3 kernel trace of the bench command"
   rm -rf $O/prof
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o trace -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-others > $O/${TAG}_prof_bench.log 2>$O/${TAG}_prof.err; echo "rocprof rc=$?"
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o trace -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-others > $O/${TAG}_prof_bench.log 2>$O/${TAG}_prof.err; echo "rocprof rc=$?"
   f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/${TAG}_bench_b32_kernel_stats.csv && head -8 "$f" | cut -c1-200
   rm -rf $O/prof
 fi
@@ -133,7 +133,7 @@ if has pmcbench; then
     rc=$?; echo "pmcbench pass [$grp] rc=$rc; rows: $(find $O/pmcb/$n -name "*counter_collection.csv" -exec cat {} + 2>/dev/null | wc -l); bench line: $(grep -o '"value": [0-9.]*' $O/pmcb/$n.log | head -1)"
     [ $rc -ne 0 ] && tail -5 $O/pmcb/$n.log | cut -c1-300
   done
-  SGMSE_PROFILE_DUMP=1 timeout 300 python bench.py --batch $PB --N 2 --steps 1 --warmup 1 --no-cpu-baseline --no-others > /dev/null 2> $O/pmcb/dump.txt
+  SGMSE_PROFILE_DUMP=1 timeout 300 python bench.py --full --batch $PB --N 2 --steps 1 --warmup 1 --no-cpu-baseline --no-others > /dev/null 2> $O/pmcb/dump.txt
   SRC_HASH=$(python -c "import bench; print(bench.source_hash())" 2>/dev/null)
   python tools/summarize_pmc_bench.py $O/pmcb/SQ_VALU_MFMA_BUSY_CYCLES $O/pmcb/SQ_LDS_BANK_CONFLICT $O/pmcb/FETCH_SIZE $O/pmcb/WRITE_SIZE --dump $O/pmcb/dump.txt \
     --meta "command=$PMCB_CMD" workload=${PMCB_WORKLOAD:-pc16k} batch=$PB "commit=${COMMIT:-unknown}" "source_hash=$SRC_HASH" > $O/${TAG}_pmc_bench_b${PB}.json 2>$O/pmcb/summ.err
@@ -149,7 +149,7 @@ fi
 if has dumps; then
   echo "== per-launch timings of one evaluation (batch 32 and batch 1)"
   for b in ${DUMP_BATCHES:-32 1}; do
-    SGMSE_PROFILE_DUMP=1 timeout 300 python bench.py --batch $b --N 2 --steps 1 --warmup 1 --no-cpu-baseline --no-others > /dev/null 2> $O/${TAG}_prof_dump_b${b}.txt
+    SGMSE_PROFILE_DUMP=1 timeout 300 python bench.py --full --batch $b --N 2 --steps 1 --warmup 1 --no-cpu-baseline --no-others > /dev/null 2> $O/${TAG}_prof_dump_b${b}.txt
     grep -c sgmse-prof $O/${TAG}_prof_dump_b${b}.txt
   done
 fi
@@ -159,7 +159,7 @@ if has lengths; then
   echo "== utterance lengths"
   : > $O/${TAG}_length_sweep.txt
   for s in ${LENGTHS:-3.0 3.5 4.0 4.5 5.0}; do
-    timeout 300 python bench.py --seconds $s --steps 2 --warmup 1 --no-others --no-cpu-baseline > $O/len_$s.json 2>/dev/null
+    timeout 300 python bench.py --full --seconds $s --steps 2 --warmup 1 --no-others --no-cpu-baseline > $O/len_$s.json 2>/dev/null
     val $O/len_$s.json "seconds=$s" | tee -a $O/${TAG}_length_sweep.txt
   done
 fi
