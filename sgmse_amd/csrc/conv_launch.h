@@ -5,6 +5,7 @@
 #include "kernels_conv1x1.h"
 #include "kernels_conv_split.h"
 #include "kernels_conv_wino.h"
+#include "kernels_conv_wino43.h"
 #include "kernels_conv_wino2d.h"
 #include "kernels_conv_thin.h"
 
@@ -186,6 +187,32 @@ inline void launch_conv_wino(const ConvArgs& a, drt::stream_t st, bool rows4, bo
     if (a.sc_w) DRT_LAUNCH((conv3x3_wino_kernel<8, 1, 1>), grid, dim3(512), st, a);
     else if (act) DRT_LAUNCH((conv3x3_wino_kernel<8, 1, 0>), grid, dim3(512), st, a);
     else DRT_LAUNCH((conv3x3_wino_kernel<8, 0, 0>), grid, dim3(512), st, a);
+  }
+}
+
+// Winograd F(4,3) x fp16x2 kernel of the wide levels (kernels_conv_wino43.h); a.w = fragments packed by pack_weights_wino43_kernel,
+// a.co_scale = the per-channel factors behind them.  rows4: the 4-row shape (same bits) for launches that cannot fill the chip.  The
+// kernel stages aligned column quads with 16-byte loads: widths are multiples of 4 and the sources 16-byte aligned.  No folded shortcut.
+inline bool conv_wino43_eligible(int C1, int C2, int Cout, int W) {
+  return Cout % 128 == 0 && (C1 + C2) % 16 == 0 && (C2 == 0 || C1 % 16 == 0) && (C1 + C2) <= 512 && W % 4 == 0;
+}
+inline bool conv_wino43_aligned(const ConvArgs& a) {
+  return reinterpret_cast<uintptr_t>(a.src1) % 16 == 0 && (a.src2 == nullptr || reinterpret_cast<uintptr_t>(a.src2) % 16 == 0);
+}
+inline void launch_conv_wino43(const ConvArgs& a, drt::stream_t st, bool rows4, bool trace = false) {
+  const bool act = a.in_scale && a.in_act;
+#ifdef SGMSE_ABLATION_FULL
+  if (trace) { DRT_LAUNCH((conv3x3_wino43_kernel<8, 1, 1>), dim3(conv_grid_tiles(a, 8), a.Cout / 128, 1), dim3(512), st, a); return; }
+#endif
+  (void)trace;
+  if (rows4) {
+    const dim3 grid(conv_grid_tiles(a, 4), a.Cout / 128, 1);
+    if (act) DRT_LAUNCH((conv3x3_wino43_kernel<4, 1>), grid, dim3(512), st, a);
+    else DRT_LAUNCH((conv3x3_wino43_kernel<4, 0>), grid, dim3(512), st, a);
+  } else {
+    const dim3 grid(conv_grid_tiles(a, 8), a.Cout / 128, 1);
+    if (act) DRT_LAUNCH((conv3x3_wino43_kernel<8, 1>), grid, dim3(512), st, a);
+    else DRT_LAUNCH((conv3x3_wino43_kernel<8, 0>), grid, dim3(512), st, a);
   }
 }
 

@@ -292,6 +292,8 @@ struct ConvW {            // one convolution's parameters on the device
   int split_mode = 0;                  // 1 bf16x3, 2 fp16x2 (0: no split layout)
   const float* packed_wino = nullptr;  // Winograd F(2,3) x fp16x2 fragment layout (kernels_conv_wino.h), 3x3 with cout % 128 == 0, cin % 16 == 0
   const float* wino_scale = nullptr;   // ... and the per-output-channel factors behind it
+  const float* packed_wino43 = nullptr;   // Winograd F(4,3) x fp16x2 fragment layout (kernels_conv_wino43.h): packed INSTEAD of packed_wino when the
+  const float* wino43_scale = nullptr;    // engine runs that form (SGMSE_WINO43), same layer class
   const float* bias = nullptr;
   int ks = 1, cin = 0, cout = 0, co_t = 0;
 };
@@ -607,6 +609,17 @@ class Engine {
       launch_conv_wino2d(a, stream_);
       SG_CHECK(drt::stream_sync(stream_));
       free_tmp(const_cast<float*>(pk)); free_tmp(bounds); free_tmp(xb);
+    } else if (force_direct == 8 || force_direct == 9) {          // Winograd F(4,3) x fp16x2: 8 = 8-row shape, 9 = 4-row shape
+      SG_REQUIRE(ks == 3 && conv_wino43_eligible(a.C1, C2, Cout, W) && conv_wino43_aligned(a), "op_conv2d: shape is not eligible for the Winograd F(4,3) kernel");
+      const float* pk = pack_wino43(w_oihw, Cin, Cout, false, &a.co_scale);
+      a.w = pk;
+      float* bounds = input_bounds(x, a.C1, x2, C2, B, H * W);
+      const float* am2 = x2 ? bounds + (size_t)B * kAmaxSpread : nullptr;
+      float* xb = producer_bound(in_scale, in_shift, Cin, bounds, am2, B);
+      a.xbound = xb;
+      launch_conv_wino43(a, stream_, force_direct == 9);
+      SG_CHECK(drt::stream_sync(stream_));
+      free_tmp(const_cast<float*>(pk)); free_tmp(bounds); free_tmp(xb);
     } else if (force_direct == 4 || force_direct == 5) {          // Winograd F(2,3) x fp16x2: 4 = 8-row shape, 5 = 4-row shape
       SG_REQUIRE(ks == 3 && conv_wino_eligible(a.C1, C2, Cout, W), "op_conv2d: shape is not eligible for the Winograd kernel");
       const float* pk = pack_wino(w_oihw, Cin, Cout, false, &a.co_scale);
@@ -732,9 +745,10 @@ class Engine {
     SG_REQUIRE(pl.mfma, "bench_conv: shape is not MFMA-eligible");
     if (variant >= 0 && (variant & 512)) { pl.rows = 4; variant &= ~512; }   // measurement knob: 128 co x 128 px tile
     int ablate = 0, abl_split = 0;
-    bool split_rows4 = false;
+    bool split_rows4 = false, wino43 = false;
     if (variant >= 0) {
       split_rows4 = (variant >> 23) & 1;         // measurement knob: 4-row workgroup shape of the split 3x3 kernel
+      wino43 = (variant >> 22) & 1;              // with bit 10: the F(4,3) form of the Winograd kernel (kernels_conv_wino43.h)
       abl_split = (variant >> 12) & 1023;        // measurement knob: compile-time variant of the split 3x3 kernel, bits 12..21
       if (!(variant & (64 | 128))) { ablate = abl_split & 15; abl_split = 0; }   // fp32 kernels: run-time ablation bits 12..15
       variant &= 4095;
@@ -745,6 +759,8 @@ class Engine {
     const bool b3 = smode != 0 && !wino && !wino2d;
     SG_REQUIRE(!(wino || wino2d) || (ks == 3 && conv_wino_eligible(Cin, 0, Cout, W)), "bench_conv: shape is not eligible for the Winograd kernel");
     SG_REQUIRE(!b3 || conv_split_eligible(ks, Cin, 0, Cout), "bench_conv: shape is not eligible for the split kernels");
+    wino43 = wino43 && wino;
+    SG_REQUIRE(!wino43 || conv_wino43_eligible(Cin, 0, Cout, W), "bench_conv: shape is not eligible for the Winograd F(4,3) kernel");
     const size_t nx = (size_t)B * Cin * H * W, no = (size_t)B * Cout * H * W, nw = (size_t)Cout * Cin * ks * ks;
     const size_t ne = packed_weight_elems(ks, Cin, Cout, pl.co_t);
     float* x = static_cast<float*>(dev_alloc_tmp(nx * 4));
@@ -781,7 +797,7 @@ class Engine {
       }
     }
     if (wino || wino2d) {
-      pk3 = wino2d ? pack_wino2d(w, Cin, Cout, false, &a.co_scale) : pack_wino(w, Cin, Cout, false, &a.co_scale); a.w = pk3;
+      pk3 = wino2d ? pack_wino2d(w, Cin, Cout, false, &a.co_scale) : wino43 ? pack_wino43(w, Cin, Cout, false, &a.co_scale) : pack_wino(w, Cin, Cout, false, &a.co_scale); a.w = pk3;
       bounds = input_bounds(x, Cin, nullptr, 0, B, H * W);
       xbound = producer_bound(a.in_scale, a.in_shift, Cin, bounds, nullptr, B); a.xbound = xbound;
     }
@@ -794,6 +810,7 @@ class Engine {
     }
     auto go = [&]() {
       if (wino2d) launch_conv_wino2d(a, stream_, abl_split & 63);
+      else if (wino43) launch_conv_wino43(a, stream_, split_rows4, (abl_split & 64) != 0);
       else if (wino) launch_conv_wino(a, stream_, split_rows4, (abl_split & 64) != 0, abl_split & 63);
       else if (b3) launch_conv_split(a, ks, smode, stream_, split_rows4, abl_split);
       else launch_conv_mfma(a, ks, pl, stream_, variant);
@@ -993,8 +1010,13 @@ class Engine {
       c.packed_split = pack_split(c.oihw, ks, cin, cout, c.split_mode, true, &c.split_scale);
     }
     if (conv_thin_eligible(ks, cin, 0, cout)) c.packed_thin = pack_thin(c.oihw, cin, cout, true);
-    // the wide levels run these layers on the Winograd F(2,3) x fp16x2 kernel (conv(): use_wino)
-    if (split_mode_ == 2 && wino_ && ks == 3 && conv_wino_eligible(cin, 0, cout, 2)) c.packed_wino = pack_wino(c.oihw, cin, cout, true, &c.wino_scale);
+    // the wide levels run these layers on a Winograd x fp16x2 kernel (conv(): use_wino): F(4,3) along the frame axis, or F(2,3) under SGMSE_WINO43=0
+    // (one form per engine: F(4,3) where SGMSE_WINO43 selects it, else F(2,3); never both packings)
+    if (split_mode_ == 2 && wino_ && ks == 3 && conv_wino_eligible(cin, 0, cout, 2)) {
+      // (the channel conditions of the two forms are the same; the width condition, W % 4 == 0, is a property of the level: conv())
+      if (wino43_ && conv_wino43_eligible(cin, 0, cout, 4)) c.packed_wino43 = pack_wino43(c.oihw, cin, cout, true, &c.wino43_scale);
+      else c.packed_wino = pack_wino(c.oihw, cin, cout, true, &c.wino_scale);
+    }
     return c;
   }
 
@@ -1038,6 +1060,20 @@ class Engine {
     DRT_LAUNCH(wino_co_scale_kernel, dim3((unsigned)((cout_pad + 255) / 256)), dim3(256), stream_, oihw, cin, cout, cout_pad, inv, sc);
     PackWinoArgs pa{oihw, pk, cin, cout, frags};
     DRT_LAUNCH(pack_weights_wino_kernel, dim3((unsigned)((frags + 255) / 256)), dim3(256), stream_, pa, (const float*)sc);
+    *scale_out = inv;
+    return reinterpret_cast<const float*>(pk);
+  }
+
+  const float* pack_wino43(const float* oihw, int cin, int cout, bool weight_owned, const float** scale_out) {
+    const size_t frags = packed_wino43_frags(cin, cout);
+    const int cout_pad = (cout + 127) / 128 * 128;
+    const size_t bytes = packed_wino43_bytes(cin, cout) + (size_t)cout_pad * 4;     // [fragments][inverse scales][scales (packing scratch)]
+    uint32_t* pk = static_cast<uint32_t*>(weight_owned ? dev_alloc_w(bytes) : dev_alloc_tmp(bytes));
+    float* inv = reinterpret_cast<float*>(pk) + frags * 4;
+    float* sc = inv + cout_pad;
+    DRT_LAUNCH(wino43_co_scale_kernel, dim3((unsigned)cout_pad), dim3(64), stream_, oihw, cin, cout, cout_pad, inv, sc);
+    PackWinoArgs pa{oihw, pk, cin, cout, frags};
+    DRT_LAUNCH(pack_weights_wino43_kernel, dim3((unsigned)((frags + 255) / 256)), dim3(256), stream_, pa, (const float*)sc);
     *scale_out = inv;
     return reinterpret_cast<const float*>(pk);
   }
@@ -1382,6 +1418,10 @@ class Engine {
     return w.packed && w.packed_split && w.split_mode == 2 && w.ks == 3 && w.cout > 32 && conv_split_eligible(3, C, 0, w.cout) &&
            (long)((H + 7) / 8) * ((W + 31) / 32) >= split_min_tiles_;
   }
+  // would conv() run this 3x3 layer on the Winograd F(4,3) kernel at this level?  (it has no folded shortcut)
+  bool runs_on_wino43(const ConvW& w, int H) const {
+    return wino_ && w.packed_wino43 && level_of(H) <= 4 && (long)((H + 7) / 8) * ((dec_W(H) + 31) / 32) >= wino_min_tiles_;
+  }
   bool shortcut_foldable(const ConvW& c2, const Tensor& a, const Tensor* b) const {
     return fold_shortcut_ && c2.packed_split && c2.split_mode == 2 && c2.ks == 1 && conv_split_eligible(1, a.C, b ? b->C : 0, c2.cout) &&
            a.amax && (!b || b->amax);
@@ -1431,13 +1471,20 @@ class Engine {
                         // raw residual stream and scale by the producers' range bounds; either must be known
                         (w.split_mode != 2 || (w.ks == 3 ? xf.bound != nullptr
                                                          : (xf.scale == nullptr && a.amax && (!b || b->amax)))));
-    // The wide levels (>= wino_min_tiles_ tiles per nominal image: 64 x 128 and up) run the full 3x3 blocks on the Winograd F(2,3) x
-    // fp16x2 kernel: 2/3 of the matrix work of the direct split kernel, which is bound by the energy of its MFMAs (kernels_conv_wino.h).
+    // The wide levels (>= wino_min_tiles_ tiles per nominal image: 64 x 128 and up) run the full 3x3 blocks on a Winograd x
+    // fp16x2 kernel: F(4,3) along the frame axis (kernels_conv_wino43.h: half of the matrix work of the direct split kernel, which is bound by the
+    // energy of its MFMAs) or, under SGMSE_WINO43=0, F(2,3) (kernels_conv_wino.h: 2/3).  One form per engine: only its weights are packed.
     // Decided per layer and level like every kernel family; its 4-row shape (launches that cannot fill the chip) gives the same bits.
-    const bool use_wino = use_split && !coarse_split && wino_ && w.packed_wino && w.ks == 3 && w.split_mode == 2 && xf.bound != nullptr &&
-                          conv_wino_eligible(a.C, b ? b->C : 0, w.cout, 2) && level_of(a.H) <= 5 && tiles8 >= wino_min_tiles_;
+    const bool use_wino = use_split && !coarse_split && wino_ && (w.packed_wino || w.packed_wino43) && w.ks == 3 && w.split_mode == 2 && xf.bound != nullptr &&
+                          conv_wino_eligible(a.C, b ? b->C : 0, w.cout, 2) && level_of(a.H) <= (w.packed_wino43 ? 4 : 5) && tiles8 >= wino_min_tiles_;
     // (the kernel stages aligned column pairs: frame counts are multiples of 64, so every utterance's width is even down to level 5)
     SG_REQUIRE(!use_wino || (a.W % 2 == 0 && (!ragged() || rag_all_mult2(a.H))), "conv: odd width on a Winograd level");
+    // The F(4,3) form stages aligned column QUADS: frame counts are multiples of 64, so every utterance's width is a multiple of 4 down to
+    // level 4 -- where SGMSE_WINO_MIN_TILES lets Winograd reach level 5, an engine that holds the F(4,3) packing runs that level on the
+    // direct split kernel (the condition above), so the requirement below cannot fail for a width the F(2,3) form would have taken.
+    // It has no folded shortcut (res_block() keeps the 1x1 its own launch on its levels: runs_on_wino43).
+    const bool use_wino43 = use_wino && w.packed_wino43 != nullptr;
+    SG_REQUIRE(!use_wino43 || (a.W % 4 == 0 && (!ragged() || rag_all_mult4(a.H)) && !sc), "conv: width not a multiple of 4 or a folded shortcut on a Winograd F(4,3) level");
     // Coarse levels (at most 512 pixels per nominal image) on the fp32 kernels: 32-channel tiles with CHUNKED accumulation (decided per
     // layer and image, never by the batch: it fixes the summation order), and -- when even those tiles leave most CUs idle
     // (small batches) -- the chunks spread over workgroups (split-K, bit-identical): a K loop of 32-64 serial stages was the
@@ -1527,7 +1574,11 @@ class Engine {
       const long nblk8 = (long)B_ * ((a.H + 7) / 8) * ((a.W + 31) / 32) * ((w.cout + 127) / 128);
       const bool rows4 = coarse_split || nblk8 < tile_min_blocks_;
       if (coarse_split) { ca.kchunk_stages = kchunk; ca.partial = partial; }
-      if (use_wino) {
+      if (use_wino43) {
+        ca.w = w.packed_wino43; ca.co_scale = w.wino43_scale; ca.acc_scale = nullptr;
+        SG_REQUIRE(conv_wino43_aligned(ca), "conv: unaligned source on a Winograd F(4,3) level");
+        launch_conv_wino43(ca, stream_, nblk8 < tile_min_blocks_);
+      } else if (use_wino) {
         ca.w = w.packed_wino; ca.co_scale = w.wino_scale; ca.acc_scale = nullptr;
         launch_conv_wino(ca, stream_, nblk8 < tile_min_blocks_);   // one 512-thread workgroup per CU: the 8-row shape from two rounds of the chip
       } else {
@@ -1537,7 +1588,7 @@ class Engine {
       if (noting()) {
         char scn[24] = "";
         if (sc) snprintf(scn, sizeof scn, " +shortcut(%d)", ca.sc_C1 + ca.sc_C2);      // (input channels of the folded 1x1)
-        snprintf(prof_note_, sizeof prof_note_, "conv3x3-%s %d->%d @%dx%dx%d%s%s%s%s", use_wino ? "wino" : "split", Cin, w.cout, B_, a.H, a.W, res ? " +res" : "",
+        snprintf(prof_note_, sizeof prof_note_, "conv3x3-%s %d->%d @%dx%dx%d%s%s%s%s", use_wino43 ? "wino43" : use_wino ? "wino" : "split", Cin, w.cout, B_, a.H, a.W, res ? " +res" : "",
                  xf.scale ? " +gn" : "", scn, ca.rag_cols ? " existing-tiles" : "");
       }
       tick(w.ks == 3 ? (w.cout >= 128 ? TC_CONV3_BIG : TC_CONV3) : TC_CONV1, fl);
@@ -1614,7 +1665,7 @@ class Engine {
     Tensor sh_t; bool sc_side = false;
     auto shortcut_early = [&](const Tensor& sa, const Tensor* sb, int Ch, int Hh) {
       if (!r.has_c2) return;
-      const bool fold = runs_on_h2_split3(r.c1, Ch, Hh, dec_W(Hh)) && shortcut_foldable(r.c2, sa, sb) && !((nofold_levels_ >> level_of(Hh)) & 1);
+      const bool fold = runs_on_h2_split3(r.c1, Ch, Hh, dec_W(Hh)) && shortcut_foldable(r.c2, sa, sb) && !((nofold_levels_ >> level_of(Hh)) & 1) && !runs_on_wino43(r.c1, Hh);
       if (fold || !side_enabled()) return;
       side_begin();
       sh_t = conv(r.c2, sa, sb, Xform{}, r.c2.bias, nullptr, nullptr, 1.f, ctl);
@@ -1640,7 +1691,7 @@ class Engine {
     if (r.has_c2) {
       const Tensor& sa = have_xs ? xs : a;
       const Tensor* sb = have_xs ? nullptr : b;
-      if (runs_on_h2_split3(r.c1, h.C, h.H, dec_W(h.H)) && shortcut_foldable(r.c2, sa, sb) && !((nofold_levels_ >> level_of(h.H)) & 1)) {
+      if (runs_on_h2_split3(r.c1, h.C, h.H, dec_W(h.H)) && shortcut_foldable(r.c2, sa, sb) && !((nofold_levels_ >> level_of(h.H)) & 1) && !runs_on_wino43(r.c1, h.H)) {
         // (Conv_1(h) + Conv_2(x)) / sqrt 2 as one accumulation: the shortcut's K-stages run inside the 3x3 launch
         const Shortcut scin{&r.c2, &sa, sb};
         out = conv(r.c1, h, nullptr, x1, r.c1.bias, nullptr, nullptr, inv_sqrt2, ctl, true, &scin);
@@ -1966,7 +2017,7 @@ class Engine {
   bool dry_ = false;
   // measurement knobs, re-read from the environment at every configure (so one process can compare settings)
   // Runtime switches, re-read from the environment at every configure / weight load (so one process can compare settings).
-  // User-facing: SGMSE_CONV_SPLIT, SGMSE_WINO, SGMSE_CONV_XCD_MAP, SGMSE_RAGGED_PREFIX, SGMSE_DEBUG_SYNC,
+  // User-facing: SGMSE_CONV_SPLIT, SGMSE_WINO, SGMSE_WINO43, SGMSE_CONV_XCD_MAP, SGMSE_RAGGED_PREFIX, SGMSE_DEBUG_SYNC,
   // SGMSE_PROFILE_DUMP.  Test hooks (what the bitwise / parity tests toggle to reach a code path; not for users):
   // SGMSE_TILE_MIN_BLOCKS, SGMSE_SPLIT_MIN_TILES, SGMSE_WINO_MIN_TILES, SGMSE_FUSE_GN_STATS, SGMSE_POISON, SGMSE_CONV_VARIANT.
   // Everything else that used to be a switch is a constant now: the losing side of each was measured and removed (round 4).
@@ -1975,7 +2026,8 @@ class Engine {
     const char* e = getenv("SGMSE_CONV_SPLIT");          // 0: fp32 MFMA only, 1: bf16x3, 2: fp16x2 (+ Winograd, see SGMSE_WINO) on the wide levels
     split_mode_ = e ? atoi(e) : SGMSE_CONV_SPLIT_DEFAULT;
     SG_REQUIRE(split_mode_ >= 0 && split_mode_ <= 2, "SGMSE_CONV_SPLIT must be 0, 1 or 2");
-    wino_ = flag("SGMSE_WINO", true);                    // Winograd F(2,3) x fp16x2 kernel on the wide levels (0: the direct fp16x2 split kernel there too)
+    wino_ = flag("SGMSE_WINO", true);                    // a Winograd x fp16x2 kernel on the wide levels (0: the direct fp16x2 split kernel there too)
+    wino43_ = flag("SGMSE_WINO43", true);                // ... in its F(4,3) form (kernels_conv_wino43.h); 0: the F(2,3) form (kernels_conv_wino.h)
     // ragged convolution launches over the tiles that exist (ConvArgs::rag_cols) and the XCD-aware tile order of the convolution
     // kernels (ConvArgs::xcd_map): both bit-identical, both measured in round 4 (profiles/r04_knobs_ab.txt: ragged batches 1.15 -> 1.04x
     // per frame; +3.5-4 % at T = 512 and T = 448) and on since
@@ -2017,7 +2069,7 @@ class Engine {
   //  launches, chunked 4-row fp16x2 kernel on the 16 x 32 / 32 x 64 levels, entry convolution on the MFMA kernel)
   static constexpr bool coarse_chunked_ = true, fold_shortcut_ = true, coarse_split_ = true, entry_mfma_ = true;
   ConvW entry8_{}; int entry8_idx_ = -1;
-  bool poison_ = false, debug_sync_ = false, conv_xcd_map_ = true, rag_prefix_ = true, wino_ = true;
+  bool poison_ = false, debug_sync_ = false, conv_xcd_map_ = true, rag_prefix_ = true, wino_ = true, wino43_ = true;
   long wino_min_tiles_ = 32;
   int nofold_levels_ = 0;
   bool lds_poison_ = false, lds_poison_upto_ = false; int lds_poison_at_ = -1, lds_poison_count_ = 0; unsigned* lds_sink_ = nullptr;

@@ -6,7 +6,8 @@ import sys
 
 import numpy as np
 
-WINO = len(sys.argv) > 2 and sys.argv[2] == "wino"
+W43 = len(sys.argv) > 2 and sys.argv[2] == "wino43"      # conv3x3_wino43_kernel<..., TRACE>: nine taps per stage, tap words at 11 / 21
+WINO = len(sys.argv) > 2 and sys.argv[2] in ("wino", "wino43")
 a = np.fromfile(sys.argv[1], dtype=np.uint64).reshape(-1, 32 if WINO else 16)
 a = a[a[:, 1] > 0]
 hw = (a[:, 0] & np.uint64(0xffffffff)).astype(np.int64)
@@ -20,14 +21,15 @@ print(f"{len(a)} workgroups; kernel span {t[:, 3].max()} cycles")
 for name, v in (("prologue", pro), ("K loop", loop), ("epilogue", epi), ("total", t[:, 3] - t[:, 0])):
     print(f"{name:9s} mean {v.mean():9.0f}  p10 {np.percentile(v, 10):9.0f}  p50 {np.percentile(v, 50):9.0f}  p90 {np.percentile(v, 90):9.0f}")
 ts = a[:, 5:15].astype(np.int64)
-if len(sys.argv) > 2 and sys.argv[2] == "wino":      # conv3x3_wino_kernel<..., TRACE>: [5] = LDS exchange, [6] = time at the stage barriers
+if WINO:      # conv3x3_wino_kernel<..., TRACE>: [5] = LDS exchange, [6] = time at the stage barriers
     print(f"output-transform exchange mean {ts[:, 0].mean():9.0f}; stage barriers (thread 0) mean {ts[:, 1].mean():9.0f} cycles")
     print("epilogue of wave 0, cycles from the end of the K loop: residual loads issued %.0f, partial sums written %.0f, barrier passed %.0f, "
           "combined %.0f, outputs stored %.0f, end %.0f" % (ts[:, 2].mean(), ts[:, 3].mean(), ts[:, 4].mean(), ts[:, 0].mean(), ts[:, 5].mean(), epi.mean()))
-    for name, off in (("A-wave (thread 0)", 16), ("B-wave (thread 256)", 23)):
-        tt = a[:, off:off + 7].astype(np.int64)
-        print(f"K loop of the {name}: cycles per tap position summed over the stages " + " ".join(f"{tt[:, i].mean():.0f}" for i in range(6)) +
-              f"; at the stage barriers {tt[:, 6].mean():.0f}")
+    NT = 9 if W43 else 6
+    for name, off in (("A-wave (thread 0)", 11 if W43 else 16), ("B-wave (thread 256)", 21 if W43 else 23)):
+        tt = a[:, off:off + NT + 1].astype(np.int64)
+        print(f"K loop of the {name}: cycles per tap position summed over the stages " + " ".join(f"{tt[:, i].mean():.0f}" for i in range(NT)) +
+              f"; at the stage barriers {tt[:, NT].mean():.0f}")
 elif ts.sum() > 0:
     tot = ts.sum(axis=1).mean()
     print("K loop of wave 0, mean time per tap position summed over the stages (share of the loop):")
