@@ -1,5 +1,6 @@
 // Launchers of the convolution kernels (tile selection happens in the engine / choose_conv_plan).
 #pragma once
+#include "conv_route.h"
 #include "kernels_conv.h"
 #include "kernels_conv_pipe.h"
 #include "kernels_conv1x1.h"
@@ -99,14 +100,9 @@ inline void launch_conv_mfma(const ConvArgs& a, int ks, const ConvPlan& pl, drt:
 #undef SGMSE_CONV_CASE
 }
 
+static_assert(ConvThinGeom::KC == kConvThinKC, "conv_thin_eligible (conv_route.h) assumes the thin kernel's stage depth");
+
 // split-operand convolutions (kernels_conv_split.h); a.w = weights packed by pack_weights_split_kernel
-inline bool conv_split_eligible(int ks, int C1, int C2, int Cout) {
-  return (ks == 3 || ks == 1) && Cout % 128 == 0 && (C1 + C2) % 16 == 0 && (C2 == 0 || C1 % 16 == 0) && (C1 + C2) <= 512;
-}
-// thin 3x3 layers (the C->4 pyramid convolutions): one zero-padded 32-channel fragment, the waves split the pixels
-inline bool conv_thin_split_eligible(int ks, int C1, int C2, int Cout) {
-  return ks == 3 && Cout <= 32 && (C1 + C2) >= 64 && (C1 + C2) % 16 == 0 && (C2 == 0 || C1 % 16 == 0) && (C1 + C2) <= 512;
-}
 // mode 1: bf16x3, mode 2: fp16x2 (a.acc_scale must point at the factor stored behind the packed weights)
 // rows4: the 4-row workgroup shape of the full 3x3 kernel (same results; for launches that cannot fill the chip)
 // abl: measurement-only ablation instantiations of the dominant shape (fp16x2, 8 rows, SiLU producer), see the kernel
@@ -122,9 +118,6 @@ inline void launch_conv3x3_split_t(const ConvArgs& a, dim3 grid, drt::stream_t s
   if (act) DRT_LAUNCH((conv3x3_split_kernel<S, SHAPE, 1>), grid, dim3(256), st, a);
   else DRT_LAUNCH((conv3x3_split_kernel<S, SHAPE, 0>), grid, dim3(256), st, a);
 }
-// rows per GroupNorm-statistics sub-tile the split kernels emit for this layer (ConvArgs::stats_rows): 4, except the thin shape
-// (two rows per wave; its layers emit no statistics in the network)
-inline int conv_split_stats_rows(int ks, int Cout) { return (ks == 3 && Cout <= 32) ? 1 : 4; }
 inline void launch_conv_split(const ConvArgs& a, int ks, int mode, drt::stream_t st, bool rows4 = false, int abl = 0, int ksplit = 1) {
   const int tiles = conv_grid_tiles(a, 8);
   if (ks == 3 && a.Cout > 32 && rows4 && a.kchunk_stages > 0 && mode == 2) {     // chunked accumulation / split-K (coarse levels)
@@ -163,68 +156,50 @@ inline void launch_conv_split(const ConvArgs& a, int ks, int mode, drt::stream_t
   if (mode == 2) launch_conv3x3_split_t<SplitH2, 0>(a, grid, st); else launch_conv3x3_split_t<SplitB3, 0>(a, grid, st);
 }
 
-// Winograd F(2,3) x fp16x2 kernel of the wide levels (kernels_conv_wino.h); a.w = fragments packed by pack_weights_wino_kernel,
-// a.co_scale = the per-channel factors behind them.  rows4: the 4-row shape (same bits) for launches that cannot fill the chip.
-inline bool conv_wino_eligible(int C1, int C2, int Cout, int W) {
-  return Cout % 128 == 0 && (C1 + C2) % 16 == 0 && (C2 == 0 || C1 % 16 == 0) && (C1 + C2) <= 512 && W % 2 == 0;
-}
-inline void launch_conv_wino(const ConvArgs& a, drt::stream_t st, bool rows4, bool trace = false, int abl = 0) {
-  const bool act = a.in_scale && a.in_act;
-#ifdef SGMSE_ABLATION_FULL
-#define SGMSE_WABL_CASE(V) if (abl == V) { DRT_LAUNCH((conv3x3_wino_kernel<8, 1, 0, 0, V>), dim3(conv_grid_tiles(a, 8), a.Cout / 128, 1), dim3(512), st, a); return; }
-  SGMSE_WABL_CASE(1) SGMSE_WABL_CASE(2) SGMSE_WABL_CASE(4) SGMSE_WABL_CASE(8) SGMSE_WABL_CASE(16) SGMSE_WABL_CASE(24) SGMSE_WABL_CASE(3) SGMSE_WABL_CASE(32) SGMSE_WABL_CASE(20)
-#undef SGMSE_WABL_CASE
-  if (trace) { DRT_LAUNCH((conv3x3_wino_kernel<8, 1, 0, 1>), dim3(conv_grid_tiles(a, 8), a.Cout / 128, 1), dim3(512), st, a); return; }
-#endif
-  (void)abl; (void)trace;
-  if (rows4) {
-    const dim3 grid(conv_grid_tiles(a, 4), a.Cout / 128, 1);
-    if (a.sc_w) DRT_LAUNCH((conv3x3_wino_kernel<4, 1, 1>), grid, dim3(512), st, a);
-    else if (act) DRT_LAUNCH((conv3x3_wino_kernel<4, 1, 0>), grid, dim3(512), st, a);
-    else DRT_LAUNCH((conv3x3_wino_kernel<4, 0, 0>), grid, dim3(512), st, a);
-  } else {
-    const dim3 grid(conv_grid_tiles(a, 8), a.Cout / 128, 1);
-    if (a.sc_w) DRT_LAUNCH((conv3x3_wino_kernel<8, 1, 1>), grid, dim3(512), st, a);
-    else if (act) DRT_LAUNCH((conv3x3_wino_kernel<8, 1, 0>), grid, dim3(512), st, a);
-    else DRT_LAUNCH((conv3x3_wino_kernel<8, 0, 0>), grid, dim3(512), st, a);
-  }
-}
-
-// Winograd F(4,3) x fp16x2 kernel of the wide levels (kernels_conv_wino43.h); a.w = fragments packed by pack_weights_wino43_kernel,
-// a.co_scale = the per-channel factors behind them.  rows4: the 4-row shape (same bits) for launches that cannot fill the chip.  The
-// kernel stages aligned column quads with 16-byte loads: widths are multiples of 4 and the sources 16-byte aligned.  No folded shortcut.
-inline bool conv_wino43_eligible(int C1, int C2, int Cout, int W) {
-  return Cout % 128 == 0 && (C1 + C2) % 16 == 0 && (C2 == 0 || C1 % 16 == 0) && (C1 + C2) <= 512 && W % 4 == 0;
-}
+// The Winograd x fp16x2 kernels of the wide levels: F(2,3) (kernels_conv_wino.h) and F(4,3) along the frame axis (kernels_conv_wino43.h);
+// a.w = fragments packed by Engine::pack_wino in that form, a.co_scale = the per-channel factors behind them.  One dispatch for both:
+// rows (8, or the 4-row shape -- same bits -- for launches that cannot fill the chip) x producer activation (x folded shortcut, F(2,3) only).
+// F(4,3) stages aligned column quads with 16-byte loads: widths are multiples of 4 and the sources 16-byte aligned (conv_wino43_aligned).
 inline bool conv_wino43_aligned(const ConvArgs& a) {
   return reinterpret_cast<uintptr_t>(a.src1) % 16 == 0 && (a.src2 == nullptr || reinterpret_cast<uintptr_t>(a.src2) % 16 == 0);
 }
-inline void launch_conv_wino43(const ConvArgs& a, drt::stream_t st, bool rows4, bool trace = false) {
+template <int ROWS>
+inline void launch_conv_wino_rows(WinoForm form, const ConvArgs& a, drt::stream_t st) {
+  const dim3 grid(conv_grid_tiles(a, ROWS), a.Cout / 128, 1);
   const bool act = a.in_scale && a.in_act;
-#ifdef SGMSE_ABLATION_FULL
-  if (trace) { DRT_LAUNCH((conv3x3_wino43_kernel<8, 1, 1>), dim3(conv_grid_tiles(a, 8), a.Cout / 128, 1), dim3(512), st, a); return; }
-#endif
-  (void)trace;
-  if (rows4) {
-    const dim3 grid(conv_grid_tiles(a, 4), a.Cout / 128, 1);
-    if (act) DRT_LAUNCH((conv3x3_wino43_kernel<4, 1>), grid, dim3(512), st, a);
-    else DRT_LAUNCH((conv3x3_wino43_kernel<4, 0>), grid, dim3(512), st, a);
+  if (form == WinoForm::F43) {
+    if (act) DRT_LAUNCH((conv3x3_wino43_kernel<ROWS, 1>), grid, dim3(512), st, a);
+    else DRT_LAUNCH((conv3x3_wino43_kernel<ROWS, 0>), grid, dim3(512), st, a);
   } else {
-    const dim3 grid(conv_grid_tiles(a, 8), a.Cout / 128, 1);
-    if (act) DRT_LAUNCH((conv3x3_wino43_kernel<8, 1>), grid, dim3(512), st, a);
-    else DRT_LAUNCH((conv3x3_wino43_kernel<8, 0>), grid, dim3(512), st, a);
+    if (a.sc_w) DRT_LAUNCH((conv3x3_wino_kernel<ROWS, 1, 1>), grid, dim3(512), st, a);
+    else if (act) DRT_LAUNCH((conv3x3_wino_kernel<ROWS, 1, 0>), grid, dim3(512), st, a);
+    else DRT_LAUNCH((conv3x3_wino_kernel<ROWS, 0, 0>), grid, dim3(512), st, a);
   }
 }
-
-// 2-D Winograd F(2x2,3x3) x fp16x2 (kernels_conv_wino2d.h; round 6: built, verified and measured against the 1-D kernel -- not the product
-// path); a.w = fragments packed by pack_weights_wino2d_kernel.  No folded shortcut.  abl: measurement only.
-inline void launch_conv_wino2d(const ConvArgs& a, drt::stream_t st, int abl = 0) {
-  const dim3 grid(conv_grid_tiles(a, 4), a.Cout / 128, 1);
-  const bool act = a.in_scale && a.in_act;
-  if (abl == 8) { DRT_LAUNCH((conv3x3_wino2d_kernel<1, 8>), grid, dim3(512), st, a); return; }
-  if (abl == 16) { DRT_LAUNCH((conv3x3_wino2d_kernel<1, 16>), grid, dim3(512), st, a); return; }
-  if (act) DRT_LAUNCH((conv3x3_wino2d_kernel<1>), grid, dim3(512), st, a);
-  else DRT_LAUNCH((conv3x3_wino2d_kernel<0>), grid, dim3(512), st, a);
+// The 2-D form F(2x2,3x3) (kernels_conv_wino2d.h; round 6: built, verified and measured against the 1-D kernel -- not the product path,
+// DESIGN.md section 8) has one shape and no folded shortcut.  trace / abl: measurement only (`make ABLATION=1`; abl 8 / 16: the 2-D form's variants)
+inline void launch_conv_wino(WinoForm form, const ConvArgs& a, drt::stream_t st, bool rows4, bool trace = false, int abl = 0) {
+  if (form == WinoForm::F2x2) {
+    const dim3 grid(conv_grid_tiles(a, 4), a.Cout / 128, 1);
+    if (abl == 8) DRT_LAUNCH((conv3x3_wino2d_kernel<1, 8>), grid, dim3(512), st, a);
+    else if (abl == 16) DRT_LAUNCH((conv3x3_wino2d_kernel<1, 16>), grid, dim3(512), st, a);
+    else if (a.in_scale && a.in_act) DRT_LAUNCH((conv3x3_wino2d_kernel<1>), grid, dim3(512), st, a);
+    else DRT_LAUNCH((conv3x3_wino2d_kernel<0>), grid, dim3(512), st, a);
+    return;
+  }
+#ifdef SGMSE_ABLATION_FULL
+  const dim3 grid8(conv_grid_tiles(a, 8), a.Cout / 128, 1);
+  if (form == WinoForm::F43) {
+    if (trace) { DRT_LAUNCH((conv3x3_wino43_kernel<8, 1, 1>), grid8, dim3(512), st, a); return; }
+  } else {
+#define SGMSE_WABL_CASE(V) if (abl == V) { DRT_LAUNCH((conv3x3_wino_kernel<8, 1, 0, 0, V>), grid8, dim3(512), st, a); return; }
+    SGMSE_WABL_CASE(1) SGMSE_WABL_CASE(2) SGMSE_WABL_CASE(4) SGMSE_WABL_CASE(8) SGMSE_WABL_CASE(16) SGMSE_WABL_CASE(24) SGMSE_WABL_CASE(3) SGMSE_WABL_CASE(32) SGMSE_WABL_CASE(20)
+#undef SGMSE_WABL_CASE
+    if (trace) { DRT_LAUNCH((conv3x3_wino_kernel<8, 1, 0, 1>), grid8, dim3(512), st, a); return; }
+  }
+#endif
+  (void)abl; (void)trace;
+  if (rows4) launch_conv_wino_rows<4>(form, a, st); else launch_conv_wino_rows<8>(form, a, st);
 }
 
 // exact-fp32 VALU kernel of the C -> 4 pyramid convolutions (kernels_conv_thin.h); a.w = weights packed by pack_weights_thin_kernel

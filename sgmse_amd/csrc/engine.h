@@ -290,10 +290,9 @@ struct ConvW {            // one convolution's parameters on the device
                                        // 3x3 with cout % 128 == 0, cin % 16 == 0
   const float* split_scale = nullptr;  // fp16x2: per output channel the factor undoing its weights' power-of-two scale (table behind the fragments)
   int split_mode = 0;                  // 1 bf16x3, 2 fp16x2 (0: no split layout)
-  const float* packed_wino = nullptr;  // Winograd F(2,3) x fp16x2 fragment layout (kernels_conv_wino.h), 3x3 with cout % 128 == 0, cin % 16 == 0
+  const float* packed_wino = nullptr;  // Winograd x fp16x2 fragment layout in the engine's ONE form (wino_form), 3x3 with cout % 128 == 0, cin % 16 == 0
   const float* wino_scale = nullptr;   // ... and the per-output-channel factors behind it
-  const float* packed_wino43 = nullptr;   // Winograd F(4,3) x fp16x2 fragment layout (kernels_conv_wino43.h): packed INSTEAD of packed_wino when the
-  const float* wino43_scale = nullptr;    // engine runs that form (SGMSE_WINO43), same layer class
+  WinoForm wino_form = WinoForm::F23;  // F43 (kernels_conv_wino43.h) where SGMSE_WINO43 selects it, else F23 (kernels_conv_wino.h)
   const float* bias = nullptr;
   int ks = 1, cin = 0, cout = 0, co_t = 0;
 };
@@ -584,6 +583,9 @@ class Engine {
     return out;
   }
 
+  // the `force_direct` argument of sgmse_op_conv2d (include/sgmse_hip.h); sgmse_amd/ops.py maps its force_split names to these values
+  enum ForceConv { FC_AUTO = 0, FC_DIRECT = 1, FC_SPLIT_B3 = 2, FC_SPLIT_H2 = 3, FC_WINO = 4, FC_WINO_4ROW = 5, FC_THIN = 6, FC_WINO2D = 7,
+                   FC_WINO43 = 8, FC_WINO43_4ROW = 9 };
   void op_conv2d(const float* x, const float* w_oihw, const float* bias, const float* res, float* out, int B, int Cin,
                  int Cout, int H, int W, int ks, float out_scale, int force_direct, const float* in_scale,
                  const float* in_shift, int in_act, const float* x2, int C2) {
@@ -591,51 +593,21 @@ class Engine {
     a.src1 = x; a.src2 = x2; a.C1 = Cin - C2; a.C2 = C2; a.bias = bias; a.res = res; a.out_scale = out_scale; a.out = out;
     a.Cout = Cout; a.B = B; a.H = H; a.W = W; a.in_scale = in_scale; a.in_shift = in_shift; a.in_act = in_act;
     ConvPlan pl = choose_conv_plan(ks, Cin, Cout, H, W);
-    if (force_direct == 6) {                               // exact-fp32 VALU kernel of the C -> 4 pyramid convolutions
+    const bool wino = force_direct == FC_WINO || force_direct == FC_WINO_4ROW || force_direct == FC_WINO2D || force_direct == FC_WINO43 || force_direct == FC_WINO43_4ROW;
+    if (force_direct == FC_THIN) {                         // exact-fp32 VALU kernel of the C -> 4 pyramid convolutions
       SG_REQUIRE(conv_thin_eligible(ks, a.C1, C2, Cout), "op_conv2d: shape is not eligible for the thin-output kernel");
       const float* pk = pack_thin(w_oihw, Cin, Cout, false);
       a.w = pk;
       launch_conv_thin(a, stream_);
       SG_CHECK(drt::stream_sync(stream_));
       free_tmp(const_cast<float*>(pk));
-    } else if (force_direct == 7) {                        // 2-D Winograd F(2x2,3x3) x fp16x2 (kernels_conv_wino2d.h)
-      SG_REQUIRE(ks == 3 && conv_wino_eligible(a.C1, C2, Cout, W), "op_conv2d: shape is not eligible for the 2-D Winograd kernel");
-      const float* pk = pack_wino2d(w_oihw, Cin, Cout, false, &a.co_scale);
-      a.w = pk;
-      float* bounds = input_bounds(x, a.C1, x2, C2, B, H * W);
-      const float* am2 = x2 ? bounds + (size_t)B * kAmaxSpread : nullptr;
-      float* xb = producer_bound(in_scale, in_shift, Cin, bounds, am2, B);
-      a.xbound = xb;
-      launch_conv_wino2d(a, stream_);
-      SG_CHECK(drt::stream_sync(stream_));
-      free_tmp(const_cast<float*>(pk)); free_tmp(bounds); free_tmp(xb);
-    } else if (force_direct == 8 || force_direct == 9) {          // Winograd F(4,3) x fp16x2: 8 = 8-row shape, 9 = 4-row shape
-      SG_REQUIRE(ks == 3 && conv_wino43_eligible(a.C1, C2, Cout, W) && conv_wino43_aligned(a), "op_conv2d: shape is not eligible for the Winograd F(4,3) kernel");
-      const float* pk = pack_wino43(w_oihw, Cin, Cout, false, &a.co_scale);
-      a.w = pk;
-      float* bounds = input_bounds(x, a.C1, x2, C2, B, H * W);
-      const float* am2 = x2 ? bounds + (size_t)B * kAmaxSpread : nullptr;
-      float* xb = producer_bound(in_scale, in_shift, Cin, bounds, am2, B);
-      a.xbound = xb;
-      launch_conv_wino43(a, stream_, force_direct == 9);
-      SG_CHECK(drt::stream_sync(stream_));
-      free_tmp(const_cast<float*>(pk)); free_tmp(bounds); free_tmp(xb);
-    } else if (force_direct == 4 || force_direct == 5) {          // Winograd F(2,3) x fp16x2: 4 = 8-row shape, 5 = 4-row shape
-      SG_REQUIRE(ks == 3 && conv_wino_eligible(a.C1, C2, Cout, W), "op_conv2d: shape is not eligible for the Winograd kernel");
-      const float* pk = pack_wino(w_oihw, Cin, Cout, false, &a.co_scale);
-      a.w = pk;
-      float* bounds = input_bounds(x, a.C1, x2, C2, B, H * W);
-      const float* am2 = x2 ? bounds + (size_t)B * kAmaxSpread : nullptr;
-      float* xb = producer_bound(in_scale, in_shift, Cin, bounds, am2, B);
-      a.xbound = xb;
-      launch_conv_wino(a, stream_, force_direct == 5);
-      SG_CHECK(drt::stream_sync(stream_));
-      free_tmp(const_cast<float*>(pk)); free_tmp(bounds); free_tmp(xb);
-    } else if (force_direct == 2 || force_direct == 3) {          // the split kernels: 2 bf16x3, 3 fp16x2
-      SG_REQUIRE(conv_split_eligible(ks, a.C1, C2, Cout) || conv_thin_split_eligible(ks, a.C1, C2, Cout),
-                 "op_conv2d: shape is not eligible for the split kernels");
-      const int smode = force_direct - 1;
-      const float* pk = pack_split(w_oihw, ks, Cin, Cout, smode, false, &a.co_scale);
+    } else if (wino || force_direct == FC_SPLIT_B3 || force_direct == FC_SPLIT_H2) {      // the Winograd x fp16x2 forms and the split kernels
+      const WinoForm form = force_direct == FC_WINO2D ? WinoForm::F2x2 : force_direct >= FC_WINO43 ? WinoForm::F43 : WinoForm::F23;
+      const int smode = wino ? 2 : force_direct - 1;       // (all Winograd forms are fp16x2)
+      if (!wino) SG_REQUIRE(conv_split_eligible(ks, a.C1, C2, Cout) || conv_thin_split_eligible(ks, a.C1, C2, Cout), "op_conv2d: shape is not eligible for the split kernels");
+      else if (form == WinoForm::F43) SG_REQUIRE(ks == 3 && conv_wino43_eligible(a.C1, C2, Cout, W) && conv_wino43_aligned(a), "op_conv2d: shape is not eligible for the Winograd F(4,3) kernel");
+      else SG_REQUIRE(ks == 3 && conv_wino_eligible(a.C1, C2, Cout, W), form == WinoForm::F2x2 ? "op_conv2d: shape is not eligible for the 2-D Winograd kernel" : "op_conv2d: shape is not eligible for the Winograd kernel");
+      const float* pk = wino ? pack_wino(form, w_oihw, Cin, Cout, false, &a.co_scale) : pack_split(w_oihw, ks, Cin, Cout, smode, false, &a.co_scale);
       a.w = pk;
       float *bounds = nullptr, *xb = nullptr;
       if (smode == 2) {      // dynamic input scale: range bounds as the producers would have left them
@@ -645,21 +617,18 @@ class Engine {
         if (ks == 1) { a.amax1 = bounds; a.amax2 = am2; }
         else { xb = producer_bound(in_scale, in_shift, Cin, bounds, am2, B); a.xbound = xb; }
       }
-      launch_conv_split(a, ks, smode, stream_);
+      if (wino) launch_conv_wino(form, a, stream_, force_direct == FC_WINO_4ROW || force_direct == FC_WINO43_4ROW);
+      else launch_conv_split(a, ks, smode, stream_);
       SG_CHECK(drt::stream_sync(stream_));
       free_tmp(const_cast<float*>(pk));
       if (bounds) free_tmp(bounds);
       if (xb) free_tmp(xb);
     } else if (pl.mfma && !force_direct && (C2 == 0 || a.C1 % ((ks == 3) ? 8 : 32) == 0)) {
-      const size_t ne = packed_weight_elems(ks, Cin, Cout, pl.co_t);
-      float* pk = static_cast<float*>(dev_alloc_tmp(ne * 4));
-      PackArgs pa{}; pa.src[0] = w_oihw; pa.nsrc = 1; pa.cout_per_src = Cout; pa.io = 0; pa.cin = Cin; pa.taps = ks * ks;
-      pa.cout = Cout; pa.co_t = pl.co_t; pa.dst = pk; pa.total = ne;
-      DRT_LAUNCH(pack_weights_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), stream_, pa);
+      const float* pk = pack_mfma(oihw_sources(w_oihw, ks, Cin, Cout), pl.co_t, false);
       a.w = pk;
       launch_conv_mfma(a, ks, pl, stream_);
       SG_CHECK(drt::stream_sync(stream_));
-      free_tmp(pk);
+      free_tmp(const_cast<float*>(pk));
     } else {
       a.w = w_oihw;
       launch_conv_direct(a, ks, stream_);
@@ -761,21 +730,18 @@ class Engine {
     SG_REQUIRE(!b3 || conv_split_eligible(ks, Cin, 0, Cout), "bench_conv: shape is not eligible for the split kernels");
     wino43 = wino43 && wino;
     SG_REQUIRE(!wino43 || conv_wino43_eligible(Cin, 0, Cout, W), "bench_conv: shape is not eligible for the Winograd F(4,3) kernel");
+    const WinoForm wform = wino2d ? WinoForm::F2x2 : wino43 ? WinoForm::F43 : WinoForm::F23;
     const size_t nx = (size_t)B * Cin * H * W, no = (size_t)B * Cout * H * W, nw = (size_t)Cout * Cin * ks * ks;
-    const size_t ne = packed_weight_elems(ks, Cin, Cout, pl.co_t);
     float* x = static_cast<float*>(dev_alloc_tmp(nx * 4));
     float* o = static_cast<float*>(dev_alloc_tmp(no * 4));
     float* r = static_cast<float*>(dev_alloc_tmp(no * 4));
     float* w = static_cast<float*>(dev_alloc_tmp(nw * 4));
-    float* pk = static_cast<float*>(dev_alloc_tmp(ne * 4));
     float* sc = static_cast<float*>(dev_alloc_tmp((size_t)B * Cin * 8));
     auto fill = [&](float* d, size_t n, uint32_t seed) {
       DRT_LAUNCH(fill_random_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), stream_, d, n, seed);
     };
     fill(x, nx, 1); fill(r, no, 2); fill(w, nw, 3); fill(sc, (size_t)B * Cin * 2, 4);
-    PackArgs pa{}; pa.src[0] = w; pa.nsrc = 1; pa.cout_per_src = Cout; pa.io = 0; pa.cin = Cin; pa.taps = ks * ks; pa.cout = Cout;
-    pa.co_t = pl.co_t; pa.dst = pk; pa.total = ne;
-    DRT_LAUNCH(pack_weights_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), stream_, pa);
+    float* pk = const_cast<float*>(pack_mfma(oihw_sources(w, ks, Cin, Cout), pl.co_t, false));
     ConvArgs a{};
     a.src1 = x; a.C1 = Cin; a.w = pk; a.out = o; a.Cout = Cout; a.B = B; a.H = H; a.W = W; a.out_scale = 1.f;
     a.ablate = ablate;
@@ -784,9 +750,9 @@ class Engine {
     drt::event_create(&e0); drt::event_create(&e1);
     const float* pk3 = nullptr;
     float *bounds = nullptr, *xbound = nullptr;
-    if (b3) {
-      pk3 = pack_split(w, ks, Cin, Cout, smode, false, &a.co_scale); a.w = pk3;
-      if (smode == 2) {
+    if (b3 || wino || wino2d) {
+      pk3 = b3 ? pack_split(w, ks, Cin, Cout, smode, false, &a.co_scale) : pack_wino(wform, w, Cin, Cout, false, &a.co_scale); a.w = pk3;
+      if (!b3 || smode == 2) {
         bounds = input_bounds(x, Cin, nullptr, 0, B, H * W);
         if (ks == 1) {
           a.in_scale = nullptr; a.in_shift = nullptr; a.in_act = 0;     // raw input, as in the network's shortcut layers
@@ -796,11 +762,6 @@ class Engine {
         }
       }
     }
-    if (wino || wino2d) {
-      pk3 = wino2d ? pack_wino2d(w, Cin, Cout, false, &a.co_scale) : wino43 ? pack_wino43(w, Cin, Cout, false, &a.co_scale) : pack_wino(w, Cin, Cout, false, &a.co_scale); a.w = pk3;
-      bounds = input_bounds(x, Cin, nullptr, 0, B, H * W);
-      xbound = producer_bound(a.in_scale, a.in_shift, Cin, bounds, nullptr, B); a.xbound = xbound;
-    }
     unsigned long long* trace_dev = nullptr;
     const size_t n_wg = (size_t)B * ((H + 7) / 8) * ((W + 31) / 32) * ((Cout + 127) / 128);
     if (abl_split & 64) {
@@ -809,9 +770,7 @@ class Engine {
       a.trace = trace_dev;
     }
     auto go = [&]() {
-      if (wino2d) launch_conv_wino2d(a, stream_, abl_split & 63);
-      else if (wino43) launch_conv_wino43(a, stream_, split_rows4, (abl_split & 64) != 0);
-      else if (wino) launch_conv_wino(a, stream_, split_rows4, (abl_split & 64) != 0, abl_split & 63);
+      if (wino || wino2d) launch_conv_wino(wform, a, stream_, split_rows4, (abl_split & 64) != 0, abl_split & 63);
       else if (b3) launch_conv_split(a, ks, smode, stream_, split_rows4, abl_split);
       else launch_conv_mfma(a, ks, pl, stream_, variant);
     };
@@ -988,19 +947,9 @@ class Engine {
     ConvPlan pl = choose_conv_plan(ks, cin, cout, 8, 32);
     if (pl.mfma) {
       c.co_t = pl.co_t;
-      const size_t ne = packed_weight_elems(ks, cin, cout, pl.co_t);
-      float* pk = static_cast<float*>(dev_alloc_w(ne * 4));
-      PackArgs pa{}; pa.src[0] = c.oihw; pa.nsrc = 1; pa.cout_per_src = cout; pa.io = 0; pa.cin = cin; pa.taps = ks * ks;
-      pa.cout = cout; pa.co_t = pl.co_t; pa.dst = pk; pa.total = ne;
-      DRT_LAUNCH(pack_weights_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), stream_, pa);
-      c.packed = pk;
-      if (pl.co_t > 32) {
-        const size_t ne32 = packed_weight_elems(ks, cin, cout, 32);
-        float* pk32 = static_cast<float*>(dev_alloc_w(ne32 * 4));
-        PackArgs pb = pa; pb.co_t = 32; pb.dst = pk32; pb.total = ne32;
-        DRT_LAUNCH(pack_weights_kernel, dim3((unsigned)((ne32 + 255) / 256)), dim3(256), stream_, pb);
-        c.packed32 = pk32;
-      }
+      const PackArgs pa = oihw_sources(c.oihw, ks, cin, cout);
+      c.packed = pack_mfma(pa, pl.co_t, true);
+      if (pl.co_t > 32) c.packed32 = pack_mfma(pa, 32, true);
     }
     // fp16x2: the input scale is a per-utterance power of two derived at run time -- 3x3 layers from the bound of their GroupNorm
     // producer's output (gn_finalize_kernel), 1x1 layers (raw residual stream) from the producers' range bounds -- the stored
@@ -1010,14 +959,25 @@ class Engine {
       c.packed_split = pack_split(c.oihw, ks, cin, cout, c.split_mode, true, &c.split_scale);
     }
     if (conv_thin_eligible(ks, cin, 0, cout)) c.packed_thin = pack_thin(c.oihw, cin, cout, true);
-    // the wide levels run these layers on a Winograd x fp16x2 kernel (conv(): use_wino): F(4,3) along the frame axis, or F(2,3) under SGMSE_WINO43=0
-    // (one form per engine: F(4,3) where SGMSE_WINO43 selects it, else F(2,3); never both packings)
+    // the wide levels run these layers on a Winograd x fp16x2 kernel (conv_route(): use_wino): F(4,3) along the frame axis, or F(2,3) under SGMSE_WINO43=0
+    // (one form per engine, decided here; the channel conditions of the two forms are the same, the width condition is a property of the level: conv_route())
     if (split_mode_ == 2 && wino_ && ks == 3 && conv_wino_eligible(cin, 0, cout, 2)) {
-      // (the channel conditions of the two forms are the same; the width condition, W % 4 == 0, is a property of the level: conv())
-      if (wino43_ && conv_wino43_eligible(cin, 0, cout, 4)) c.packed_wino43 = pack_wino43(c.oihw, cin, cout, true, &c.wino43_scale);
-      else c.packed_wino = pack_wino(c.oihw, cin, cout, true, &c.wino_scale);
+      c.wino_form = (wino43_ && conv_wino43_eligible(cin, 0, cout, 4)) ? WinoForm::F43 : WinoForm::F23;
+      c.packed_wino = pack_wino(c.wino_form, c.oihw, cin, cout, true, &c.wino_scale);
     }
     return c;
+  }
+
+  // weights in the fp32 MFMA kernels' layout (pack_weights_kernel) for co_t-channel output tiles; pa names the sources
+  static PackArgs oihw_sources(const float* oihw, int ks, int cin, int cout) {
+    PackArgs pa{}; pa.src[0] = oihw; pa.nsrc = 1; pa.cout_per_src = cout; pa.io = 0; pa.cin = cin; pa.taps = ks * ks; pa.cout = cout;
+    return pa;
+  }
+  const float* pack_mfma(PackArgs pa, int co_t, bool weight_owned) {
+    pa.co_t = co_t; pa.total = packed_weight_elems(pa.taps == 9 ? 3 : 1, pa.cin, pa.cout, co_t);
+    pa.dst = static_cast<float*>(weight_owned ? dev_alloc_w(pa.total * 4) : dev_alloc_tmp(pa.total * 4));
+    DRT_LAUNCH(pack_weights_kernel, dim3((unsigned)((pa.total + 255) / 256)), dim3(256), stream_, pa);
+    return pa.dst;
   }
 
   // weights in the fragment order of conv3x3_split_kernel (mode 1: bf16x3, 2: fp16x2 with the layer's power-of-two scale)
@@ -1043,51 +1003,35 @@ class Engine {
     return reinterpret_cast<const float*>(pk);
   }
 
-  // weights in the fragment order of conv3x3_wino_kernel: transformed along the kernel's columns in fp64, scaled per output channel
+  // weights of the C -> 4 layers as [ci][tap][4 co] (conv3x3_thin_kernel)
   const float* pack_thin(const float* oihw, int cin, int cout, bool weight_owned) {
     const size_t ne = packed_thin_elems(cin);
     float* pk = static_cast<float*>(weight_owned ? dev_alloc_w(ne * 4) : dev_alloc_tmp(ne * 4));
     DRT_LAUNCH(pack_weights_thin_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), stream_, oihw, pk, cin, cout);
     return pk;
   }
-  const float* pack_wino(const float* oihw, int cin, int cout, bool weight_owned, const float** scale_out) {
-    const size_t frags = packed_wino_frags(cin, cout);
+  // weights in the fragment order of the Winograd kernel of `form`: transformed in fp64, scaled per output channel
+  const float* pack_wino(WinoForm form, const float* oihw, int cin, int cout, bool weight_owned, const float** scale_out) {
+    const bool f43 = form == WinoForm::F43, f2d = form == WinoForm::F2x2;
+    const size_t frags = f43 ? packed_wino43_frags(cin, cout) : f2d ? packed_wino2d_frags(cin, cout) : packed_wino_frags(cin, cout);
     const int cout_pad = (cout + 127) / 128 * 128;
-    const size_t bytes = packed_wino_bytes(cin, cout) + (size_t)cout_pad * 4;       // [fragments][inverse scales][scales (packing scratch)]
+    const size_t bytes = (f43 ? packed_wino43_bytes(cin, cout) : f2d ? packed_wino2d_bytes(cin, cout) : packed_wino_bytes(cin, cout)) +
+                         (size_t)cout_pad * 4;                          // [fragments][inverse scales][scales (packing scratch)]
     uint32_t* pk = static_cast<uint32_t*>(weight_owned ? dev_alloc_w(bytes) : dev_alloc_tmp(bytes));
     float* inv = reinterpret_cast<float*>(pk) + frags * 4;
     float* sc = inv + cout_pad;
-    DRT_LAUNCH(wino_co_scale_kernel, dim3((unsigned)((cout_pad + 255) / 256)), dim3(256), stream_, oihw, cin, cout, cout_pad, inv, sc);
-    PackWinoArgs pa{oihw, pk, cin, cout, frags};
-    DRT_LAUNCH(pack_weights_wino_kernel, dim3((unsigned)((frags + 255) / 256)), dim3(256), stream_, pa, (const float*)sc);
-    *scale_out = inv;
-    return reinterpret_cast<const float*>(pk);
-  }
-
-  const float* pack_wino43(const float* oihw, int cin, int cout, bool weight_owned, const float** scale_out) {
-    const size_t frags = packed_wino43_frags(cin, cout);
-    const int cout_pad = (cout + 127) / 128 * 128;
-    const size_t bytes = packed_wino43_bytes(cin, cout) + (size_t)cout_pad * 4;     // [fragments][inverse scales][scales (packing scratch)]
-    uint32_t* pk = static_cast<uint32_t*>(weight_owned ? dev_alloc_w(bytes) : dev_alloc_tmp(bytes));
-    float* inv = reinterpret_cast<float*>(pk) + frags * 4;
-    float* sc = inv + cout_pad;
-    DRT_LAUNCH(wino43_co_scale_kernel, dim3((unsigned)cout_pad), dim3(64), stream_, oihw, cin, cout, cout_pad, inv, sc);
-    PackWinoArgs pa{oihw, pk, cin, cout, frags};
-    DRT_LAUNCH(pack_weights_wino43_kernel, dim3((unsigned)((frags + 255) / 256)), dim3(256), stream_, pa, (const float*)sc);
-    *scale_out = inv;
-    return reinterpret_cast<const float*>(pk);
-  }
-
-  const float* pack_wino2d(const float* oihw, int cin, int cout, bool weight_owned, const float** scale_out) {
-    const size_t frags = packed_wino2d_frags(cin, cout);
-    const int cout_pad = (cout + 127) / 128 * 128;
-    const size_t bytes = packed_wino2d_bytes(cin, cout) + (size_t)cout_pad * 4;     // [fragments][inverse scales][scales (packing scratch)]
-    uint32_t* pk = static_cast<uint32_t*>(weight_owned ? dev_alloc_w(bytes) : dev_alloc_tmp(bytes));
-    float* inv = reinterpret_cast<float*>(pk) + frags * 4;
-    float* sc = inv + cout_pad;
-    DRT_LAUNCH(wino2d_co_scale_kernel, dim3((unsigned)((cout_pad + 255) / 256)), dim3(256), stream_, oihw, cin, cout, cout_pad, inv, sc);
-    PackWinoArgs pa{oihw, pk, cin, cout, frags};
-    DRT_LAUNCH(pack_weights_wino2d_kernel, dim3((unsigned)((frags + 255) / 256)), dim3(256), stream_, pa, (const float*)sc);
+    const PackWinoArgs pa{oihw, pk, cin, cout, frags};
+    const dim3 gs((unsigned)((cout_pad + 255) / 256)), gp((unsigned)((frags + 255) / 256));
+    if (f43) {              // (one wave per output channel)
+      DRT_LAUNCH(wino43_co_scale_kernel, dim3((unsigned)cout_pad), dim3(64), stream_, oihw, cin, cout, cout_pad, inv, sc);
+      DRT_LAUNCH(pack_weights_wino43_kernel, gp, dim3(256), stream_, pa, (const float*)sc);
+    } else if (f2d) {
+      DRT_LAUNCH(wino2d_co_scale_kernel, gs, dim3(256), stream_, oihw, cin, cout, cout_pad, inv, sc);
+      DRT_LAUNCH(pack_weights_wino2d_kernel, gp, dim3(256), stream_, pa, (const float*)sc);
+    } else {
+      DRT_LAUNCH(wino_co_scale_kernel, gs, dim3(256), stream_, oihw, cin, cout, cout_pad, inv, sc);
+      DRT_LAUNCH(pack_weights_wino_kernel, gp, dim3(256), stream_, pa, (const float*)sc);
+    }
     *scale_out = inv;
     return reinterpret_cast<const float*>(pk);
   }
@@ -1106,26 +1050,16 @@ class Engine {
     ConvPlan pl = choose_conv_plan(1, C, c.cout, 8, 32);
     if (pl.mfma) {
       c.co_t = pl.co_t;
-      const size_t ne = packed_weight_elems(1, C, c.cout, pl.co_t);
-      float* pk = static_cast<float*>(dev_alloc_w(ne * 4));
-      PackArgs pa{}; pa.nsrc = nsrc; pa.cout_per_src = C; pa.io = 1; pa.cin = C; pa.taps = 1; pa.cout = c.cout; pa.co_t = pl.co_t;
-      pa.dst = pk; pa.total = ne;
+      PackArgs pa{}; pa.nsrc = nsrc; pa.cout_per_src = C; pa.io = 1; pa.cin = C; pa.taps = 1; pa.cout = c.cout;
       for (int s = 0; s < nsrc; ++s) pa.src[s] = Wp(pre + "NIN_" + std::to_string(which[s]) + ".W");
-      DRT_LAUNCH(pack_weights_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), stream_, pa);
-      c.packed = pk;
+      c.packed = pack_mfma(pa, pl.co_t, true);
       // (round 5) the 32-channel-tile layout too, as make_conv does: the attention projections sit at the 16 x 32 and 4 x 8 levels, where
       // conv() runs the fp32 layers on 32-channel tiles with chunked accumulation and, at small batches, split-K -- without this layout
       // q|k|v and the output projection stayed on 128-channel tiles: 24 / 8 workgroups running 16 serial K-stages at batch 1
       // (31 / 30 us per launch against 18 us for the 1x1 shortcut of the same size, profiles/r05_prof_dump_b1.txt)
       // (round 6: the compile-time switch of round 5's A/B is gone -- one build variant, the tested one.  Attention outputs changed in
       //  their last bits with that round: fixtures of these levels recorded before it are not bit-comparable.)
-      if (pl.co_t > 32) {
-        const size_t ne32 = packed_weight_elems(1, C, c.cout, 32);
-        float* pk32 = static_cast<float*>(dev_alloc_w(ne32 * 4));
-        PackArgs pb = pa; pb.co_t = 32; pb.dst = pk32; pb.total = ne32;
-        DRT_LAUNCH(pack_weights_kernel, dim3((unsigned)((ne32 + 255) / 256)), dim3(256), stream_, pb);
-        c.packed32 = pk32;
-      }
+      if (pl.co_t > 32) c.packed32 = pack_mfma(pa, 32, true);
     }
     if (split_mode_ && conv_split_eligible(1, C, 0, c.cout)) {
       c.split_mode = 1;
@@ -1314,16 +1248,9 @@ class Engine {
     const int l = level_of(H);
     return Rag{rag_w_dev_.at(l), rag_off_dev_.at(l), rag_soff_dev_.at(l)};
   }
-  bool rag_all_mult2(int H) const {
-    if (!ragged()) return true;
+  bool rag_all_mult(int H, int m) const {          // a ragged batch: is every utterance's width at this level a multiple of m?  (uniform batches: yes, the caller checks W)
     const int l = level_of(H);
-    for (int t : rag_T_) if ((t >> l) % 2) return false;
-    return true;
-  }
-  bool rag_all_mult4(int H) const {
-    if (!ragged()) return true;
-    const int l = level_of(H);
-    for (int t : rag_T_) if ((t >> l) % 4) return false;
+    for (int t : rag_T_) if ((t >> l) % m) return false;
     return true;
   }
   void set_frames(const int* frames, int n) {          // n == 0: uniform batches again
@@ -1413,111 +1340,37 @@ class Engine {
 
   // residual shortcut folded into a 3x3 split launch (ConvArgs::sc_*): the 1x1 layer and its (raw) input
   struct Shortcut { const ConvW* w; const Tensor* a; const Tensor* b; };
-  // would conv() run this 3x3 layer (GroupNorm producer in front) on the fp16x2 split kernel at this level?  (the rule below; W = dec_W)
-  bool runs_on_h2_split3(const ConvW& w, int C, int H, int W) const {
-    return w.packed && w.packed_split && w.split_mode == 2 && w.ks == 3 && w.cout > 32 && conv_split_eligible(3, C, 0, w.cout) &&
-           (long)((H + 7) / 8) * ((W + 31) / 32) >= split_min_tiles_;
-  }
-  // would conv() run this 3x3 layer on the Winograd F(4,3) kernel at this level?  (it has no folded shortcut)
-  bool runs_on_wino43(const ConvW& w, int H) const {
-    return wino_ && w.packed_wino43 && level_of(H) <= 4 && (long)((H + 7) / 8) * ((dec_W(H) + 31) / 32) >= wino_min_tiles_;
-  }
+  // may this 1x1 shortcut be folded at all: split-packed in fp16x2, with known input ranges
   bool shortcut_foldable(const ConvW& c2, const Tensor& a, const Tensor* b) const {
     return fold_shortcut_ && c2.packed_split && c2.split_mode == 2 && c2.ks == 1 && conv_split_eligible(1, a.C, b ? b->C : 0, c2.cout) &&
            a.amax && (!b || b->amax);
   }
 
+  // the route of one convolution (conv_route.h) from the layer, the level of its input and what the call brings
+  ConvRoute route_of(const ConvW& w, int C1, int C2, int H, int W, const ConvCall& call) const {
+    const ConvLayer layer{w.ks, C1, C2, w.cout, w.co_t, w.packed != nullptr, w.packed32 != nullptr, w.packed_thin != nullptr,
+                          w.packed_split != nullptr, w.packed_wino != nullptr, w.split_mode, w.wino_form};
+    const ConvKnobs knobs{tile_min_blocks_, split_min_tiles_, wino_min_tiles_, wino_, fuse_gn_stats_, chunk_max_tiles_, coarse_splitk_div_,
+                          coarse_chunked_, coarse_split_};
+    return conv_route(layer, ConvLevel{H, W, dec_W(H), level_of(H)}, call, B_, knobs);
+  }
+
   Tensor conv(const ConvW& w, const Tensor& a, const Tensor* b, const Xform& xf, const float* bias, const float* bias2,
               const float* res, float out_scale, const FwdCtl& ctl, bool emit_stats = false, const Shortcut* sc = nullptr) {
-    const int Cin = a.C + (b ? b->C : 0);
+    const int C2 = b ? b->C : 0, Cin = a.C + C2;
     SG_REQUIRE(Cin == w.cin, "conv: channel mismatch");
     Tensor o = new_tensor(w.cout, a.H, a.W);
-    const int kc_ = (w.ks == 3) ? 8 : 32;
-    const bool use_mfma = w.packed && (b == nullptr || a.C % kc_ == 0);
-    // tile choice: the most efficient tile (widest channel block, 8 rows) that still gives the chip enough workgroups
-    // (tile_min_blocks_, 2 per CU), falling back towards 32 channels x 4 rows for the coarse U-Net levels and for small
-    // batches.  All tile shapes accumulate every output in the same order and emit the same per-row GroupNorm partials
-    // (kernels_conv.h), so the choice -- and with it the batch size -- never changes a result bit.
-    int co_t = w.co_t, rows_ = a.H >= 8 ? 8 : 4;
-    if (use_mfma) {
-      const int cand_co[2] = {w.co_t, w.packed32 ? 32 : w.co_t};
-      long best = -1;
-      bool done = false;
-      for (int ci = 0; ci < 2 && !done; ++ci)
-        for (int rows = (a.H >= 8 ? 8 : 4); rows >= 4 && !done; rows -= 4) {
-          if (ci == 1 && cand_co[1] == cand_co[0]) break;
-          const long nblk = (long)B_ * ((a.H + rows - 1) / rows) * ((a.W + 31) / 32) * ((w.cout + cand_co[ci] - 1) / cand_co[ci]);
-          if (nblk > best) { best = nblk; co_t = cand_co[ci]; rows_ = rows; }
-          if (nblk >= tile_min_blocks_) done = true;
-        }
-    }
-    // fp32-accurate bf16x3 kernel for the wide levels.  Decided per layer and per LEVEL (never by the batch size or the utterance length), because
-    // its results differ from the fp32-MFMA kernels in the last bits and an utterance must not depend on its batch.
-    const int Wd = dec_W(a.H);          // family decisions by the level, not by the utterance length (see dec_W)
-    const long tiles8 = (long)((a.H + 7) / 8) * ((Wd + 31) / 32);
-    // Levels with at most chunk_max_tiles_ tiles per nominal image (32 x 64 and below): the fp16x2 split kernel in its 4-row shape with
-    // CHUNKED accumulation, so that a small batch can spread the chunks over workgroups (split-K, bit-identical) instead of running 16-32
-    // serial stages on 8-32 workgroups; full 3x3 blocks behind a GroupNorm producer only (not the launches with a folded
-    // shortcut).  Decided per layer and level, never by the batch or the utterance length: chunking fixes the summation order.
-    // The 8 x 16 and 4 x 8 levels joined in round 4: their tiles are half / three quarters empty, yet at batch 32 the layers take 0.057 /
-    // 0.038 ms against 0.115 / 0.065 ms on the fp32 kernels (+1.7 % utterances/s); a single utterance pays 9 us per layer for the
-    // four times wider output tile of a workgroup (434 -> 452 ms per utterance at batch 1; profiles/r04_coarse_levels.txt).
-    const bool coarse_split = coarse_split_ && use_mfma && w.packed_split && w.split_mode == 2 && w.ks == 3 && w.cout > 32 && !sc &&
-                              conv_split_eligible(3, a.C, b ? b->C : 0, w.cout) && tiles8 <= chunk_max_tiles_ && xf.bound != nullptr;
-    const bool use_split = coarse_split || (use_mfma && w.packed_split &&
-                        (conv_split_eligible(w.ks, a.C, b ? b->C : 0, w.cout) || conv_thin_split_eligible(w.ks, a.C, b ? b->C : 0, w.cout)) &&
-                        tiles8 >= split_min_tiles_ &&
-                        // fp16x2: 3x3 layers scale by the bound of their GroupNorm producer's output, 1x1 layers read the
-                        // raw residual stream and scale by the producers' range bounds; either must be known
-                        (w.split_mode != 2 || (w.ks == 3 ? xf.bound != nullptr
-                                                         : (xf.scale == nullptr && a.amax && (!b || b->amax)))));
-    // The wide levels (>= wino_min_tiles_ tiles per nominal image: 64 x 128 and up) run the full 3x3 blocks on a Winograd x
-    // fp16x2 kernel: F(4,3) along the frame axis (kernels_conv_wino43.h: half of the matrix work of the direct split kernel, which is bound by the
-    // energy of its MFMAs) or, under SGMSE_WINO43=0, F(2,3) (kernels_conv_wino.h: 2/3).  One form per engine: only its weights are packed.
-    // Decided per layer and level like every kernel family; its 4-row shape (launches that cannot fill the chip) gives the same bits.
-    const bool use_wino = use_split && !coarse_split && wino_ && (w.packed_wino || w.packed_wino43) && w.ks == 3 && w.split_mode == 2 && xf.bound != nullptr &&
-                          conv_wino_eligible(a.C, b ? b->C : 0, w.cout, 2) && level_of(a.H) <= (w.packed_wino43 ? 4 : 5) && tiles8 >= wino_min_tiles_;
-    // (the kernel stages aligned column pairs: frame counts are multiples of 64, so every utterance's width is even down to level 5)
-    SG_REQUIRE(!use_wino || (a.W % 2 == 0 && (!ragged() || rag_all_mult2(a.H))), "conv: odd width on a Winograd level");
-    // The F(4,3) form stages aligned column QUADS: frame counts are multiples of 64, so every utterance's width is a multiple of 4 down to
-    // level 4 -- where SGMSE_WINO_MIN_TILES lets Winograd reach level 5, an engine that holds the F(4,3) packing runs that level on the
-    // direct split kernel (the condition above), so the requirement below cannot fail for a width the F(2,3) form would have taken.
-    // It has no folded shortcut (res_block() keeps the 1x1 its own launch on its levels: runs_on_wino43).
-    const bool use_wino43 = use_wino && w.packed_wino43 != nullptr;
-    SG_REQUIRE(!use_wino43 || (a.W % 4 == 0 && (!ragged() || rag_all_mult4(a.H)) && !sc), "conv: width not a multiple of 4 or a folded shortcut on a Winograd F(4,3) level");
-    // Coarse levels (at most 512 pixels per nominal image) on the fp32 kernels: 32-channel tiles with CHUNKED accumulation (decided per
-    // layer and image, never by the batch: it fixes the summation order), and -- when even those tiles leave most CUs idle
-    // (small batches) -- the chunks spread over workgroups (split-K, bit-identical): a K loop of 32-64 serial stages was the
-    // latency of these launches (60-120 us each at batch 1, profiles/r02_prof_dump_b1_per_launch.txt)
-    int kchunk = 0, ksplit = 1;
-    float* partial = nullptr;
-    if (coarse_split) {
-      const int nstages = Cin / 16;
-      kchunk = std::max(2, (nstages + 7) / 8);
-      const int nchunks = (nstages + kchunk - 1) / kchunk;
-      const long nblk = (long)B_ * ((a.H + 3) / 4) * ((a.W + 31) / 32) * (w.cout / 128);
-      if (nchunks > 1 && nblk * coarse_splitk_div_ <= tile_min_blocks_) {
-        ksplit = nchunks;
-        partial = arena_.alloc((size_t)nchunks * w.cout * pix_total(a.H, a.W));
-      }
-    }
-    if (use_mfma && !use_split && coarse_chunked_ && (long)a.H * Wd <= 512 && (w.co_t == 32 || w.packed32)) {
-      co_t = 32;
-      const long nblk8 = (long)B_ * ((a.H + 7) / 8) * ((a.W + 31) / 32) * ((w.cout + 31) / 32);
-      rows_ = (a.H >= 8 && nblk8 >= tile_min_blocks_) ? 8 : 4;
-      const int nstages = Cin / kc_;
-      kchunk = std::max(w.ks == 3 ? 4 : 2, (nstages + 7) / 8);
-      const int nchunks = (nstages + kchunk - 1) / kchunk;
-      const long nblk = (long)B_ * ((a.H + rows_ - 1) / rows_) * ((a.W + 31) / 32) * ((w.cout + 31) / 32);
-      if (nchunks > 1 && nblk * 2 <= tile_min_blocks_) {
-        ksplit = nchunks;
-        partial = arena_.alloc((size_t)nchunks * w.cout * pix_total(a.H, a.W));
-      }
-    }
-    if (emit_stats && use_mfma && fuse_gn_stats_) {
-      // the split kernels emit one partial pair per 4 image rows, the fp32 kernels one per row (ConvArgs::stats_rows): a property
-      // of the kernel family, which is a property of the layer and level
-      o.srows = use_split ? conv_split_stats_rows(w.ks, w.cout) : 1;
+    const ConvRoute rt = route_of(w, a.C, C2, a.H, a.W, ConvCall{xf.bound != nullptr, a.amax && (!b || b->amax), xf.scale != nullptr, emit_stats,
+                                                                 bias2 != nullptr, sc != nullptr});
+    const ConvFamily fam = rt.family;
+    // what the route's kernels need of the actual widths and of the call: checks on the route (the family is decided by the level alone)
+    SG_REQUIRE(fam != ConvFamily::Wino23 || (a.W % 2 == 0 && rag_all_mult(a.H, 2)), "conv: odd width on a Winograd level");
+    SG_REQUIRE(fam != ConvFamily::Wino43 || (a.W % 4 == 0 && rag_all_mult(a.H, 4)), "conv: width not a multiple of 4 on a Winograd F(4,3) level");
+    SG_REQUIRE(!sc || (rt.accepts_shortcut && xf.act && !res), "conv: shortcut fold on an ineligible launch");
+    // ---- allocate: split-K partial sums, GroupNorm statistics, the range-bound slot
+    float* partial = rt.ksplit > 1 ? arena_.alloc((size_t)rt.ksplit * w.cout * pix_total(a.H, a.W)) : nullptr;
+    if (emit_stats && fuse_gn_stats_ && fam != ConvFamily::Direct) {
+      o.srows = rt.srows;
       SG_REQUIRE(o.srows == 1 || !ragged() || a.H % 4 == 0, "ragged batch: 4-row statistics sub-tiles need H % 4 == 0");
       o.nsub = conv_plan_nsub(a.H, a.W, o.srows);
       o.st = arena_.alloc((size_t)B_ * w.cout * o.nsub * 2);
@@ -1533,21 +1386,20 @@ class Engine {
     ca.xcd_map = conv_xcd_map_ ? 1 : 0;
     ca.stats_out = o.st; ca.stats_nsub = o.nsub; ca.stats_rows = o.srows;
     ca.amax_out = o.amax;
-    ca.src1 = a.p; ca.src2 = b ? b->p : nullptr; ca.C1 = a.C; ca.C2 = b ? b->C : 0;
+    ca.src1 = a.p; ca.src2 = b ? b->p : nullptr; ca.C1 = a.C; ca.C2 = C2;
     ca.bias = bias; ca.bias2 = bias2; ca.bias2_bstride = ctl.bias_bstride; ca.bias2_sstride = ctl.bias_sstride;
     ca.step_ptr = bias2 ? ctl.bias_step : nullptr;
     ca.in_scale = xf.scale; ca.in_shift = xf.shift; ca.in_act = xf.act;
     ca.res = res; ca.out_scale = out_scale; ca.out = o.p; ca.Cout = w.cout; ca.B = B_; ca.H = a.H; ca.W = a.W;
+    ca.kchunk_stages = rt.kchunk; ca.partial = partial;
     if (ragged()) {
       const Rag rg = rag_of(a.H);
       ca.rag_w = rg.w; ca.rag_off = rg.off; ca.rag_soff = rg.soff; ca.rag_slab = (long long)w.cout * (long long)pix_total(a.H, a.W);
-      ca.rag_vec_ok = rag_all_mult4(a.H) ? 1 : 0;
+      ca.rag_vec_ok = rag_all_mult(a.H, 4) ? 1 : 0;
       if (rag_prefix_) { const int l = level_of(a.H); ca.rag_cols = rag_cols_dev_.at(l); ca.rag_ncols = rag_ncols_.at(l); }
     }
-    tock();
     double fl = 2.0 * B_ * (double)w.cout * Cin * w.ks * w.ks * a.H * a.W;
     if (sc) {
-      SG_REQUIRE(use_split && w.ks == 3 && w.split_mode == 2 && w.cout > 32 && xf.scale && xf.act && !res, "conv: shortcut fold on an ineligible launch");
       const int Cs = sc->a->C + (sc->b ? sc->b->C : 0);
       SG_REQUIRE(Cs == sc->w->cin && sc->w->cout == w.cout && sc->a->H == a.H && sc->a->W == a.W, "conv: shortcut shape mismatch");
       ca.sc_src1 = sc->a->p; ca.sc_src2 = sc->b ? sc->b->p : nullptr; ca.sc_C1 = sc->a->C; ca.sc_C2 = sc->b ? sc->b->C : 0;
@@ -1555,67 +1407,64 @@ class Engine {
       ca.sc_amax1 = sc->a->amax; ca.sc_amax2 = sc->b ? sc->b->amax : nullptr;
       fl += 2.0 * B_ * (double)w.cout * Cs * a.H * a.W;
     }
-    // the C -> 4 convolutions of the output pyramid: exact-fp32 VALU kernel (kernels_conv_thin.h) -- on the matrix pipe
-    // seven eighths of their work was padding (decided by the layer's shape and U-Net level alone: never by batch or utterance length)
-    // (the two finest levels: below them a launch at batch 1 has few 16 x 64 tiles and their 32-64 serial stages are slower than the MFMA path's split-K)
-    // (conv3x3_thin_kernel has no time-embedding row, accumulator scale or folded shortcut: a layer that carries one stays on the MFMA shapes)
-    const bool use_thin = w.packed_thin && conv_thin_eligible(w.ks, a.C, b ? b->C : 0, w.cout) && !emit_stats && level_of(a.H) <= 1 && !bias2 && !sc;
-    if (use_thin) {
-      ca.w = w.packed_thin; ca.stats_out = nullptr;
-      launch_conv_thin(ca, stream_);
-      if (noting()) snprintf(prof_note_, sizeof prof_note_, "conv3x3-thin %d->%d @%dx%dx%d%s%s", Cin, w.cout, B_, a.H, a.W, res ? " +res" : "", xf.scale ? " +gn" : "");
-      tick(TC_CONV3, fl);
-      if (partial) arena_.release(partial);
-    } else if (use_split) {
-      ca.w = w.packed_split; ca.co_scale = w.split_scale;      // (null for bf16x3: no scale)
-      if (w.ks == 1 && w.split_mode == 2) { ca.amax1 = a.amax; ca.amax2 = b ? b->amax : nullptr; }
-      if (w.ks == 3 && w.split_mode == 2) ca.xbound = xf.bound;
-      // 4-row workgroups when 8-row ones would leave CUs idle (bit-identical results, so this may follow the batch size)
-      const long nblk8 = (long)B_ * ((a.H + 7) / 8) * ((a.W + 31) / 32) * ((w.cout + 127) / 128);
-      const bool rows4 = coarse_split || nblk8 < tile_min_blocks_;
-      if (coarse_split) { ca.kchunk_stages = kchunk; ca.partial = partial; }
-      if (use_wino43) {
-        ca.w = w.packed_wino43; ca.co_scale = w.wino43_scale; ca.acc_scale = nullptr;
+    tock();
+    const char* gn = xf.scale ? " +gn" : "";
+    const char* rs = res ? " +res" : "";
+    const char* ex = ca.rag_cols ? " existing-tiles" : "";
+    auto note_split = [&](const char* name) {        // the split and Winograd families
+      if (!noting()) return;
+      char scn[24] = "";
+      if (sc) snprintf(scn, sizeof scn, " +shortcut(%d)", ca.sc_C1 + ca.sc_C2);      // (input channels of the folded 1x1)
+      snprintf(prof_note_, sizeof prof_note_, "conv3x3-%s %d->%d @%dx%dx%d%s%s%s%s", name, Cin, w.cout, B_, a.H, a.W, rs, gn, scn, ex);
+    };
+    int cls = w.ks == 3 ? (w.cout >= 128 ? TC_CONV3_BIG : TC_CONV3) : TC_CONV1;      // (the split and Winograd families)
+    switch (fam) {
+      case ConvFamily::Thin:
+        ca.w = w.packed_thin; ca.stats_out = nullptr;
+        launch_conv_thin(ca, stream_);
+        if (noting()) snprintf(prof_note_, sizeof prof_note_, "conv3x3-thin %d->%d @%dx%dx%d%s%s", Cin, w.cout, B_, a.H, a.W, rs, gn);
+        cls = TC_CONV3;
+        break;
+      case ConvFamily::Wino43:
         SG_REQUIRE(conv_wino43_aligned(ca), "conv: unaligned source on a Winograd F(4,3) level");
-        launch_conv_wino43(ca, stream_, nblk8 < tile_min_blocks_);
-      } else if (use_wino) {
-        ca.w = w.packed_wino; ca.co_scale = w.wino_scale; ca.acc_scale = nullptr;
-        launch_conv_wino(ca, stream_, nblk8 < tile_min_blocks_);   // one 512-thread workgroup per CU: the 8-row shape from two rounds of the chip
-      } else {
-        launch_conv_split(ca, w.ks, w.split_mode, stream_, rows4, 0, ksplit);
-      }
-      if (coarse_split && partial) arena_.release(partial);
-      if (noting()) {
-        char scn[24] = "";
-        if (sc) snprintf(scn, sizeof scn, " +shortcut(%d)", ca.sc_C1 + ca.sc_C2);      // (input channels of the folded 1x1)
-        snprintf(prof_note_, sizeof prof_note_, "conv3x3-%s %d->%d @%dx%dx%d%s%s%s%s", use_wino43 ? "wino43" : use_wino ? "wino" : "split", Cin, w.cout, B_, a.H, a.W, res ? " +res" : "",
-                 xf.scale ? " +gn" : "", scn, ca.rag_cols ? " existing-tiles" : "");
-      }
-      tick(w.ks == 3 ? (w.cout >= 128 ? TC_CONV3_BIG : TC_CONV3) : TC_CONV1, fl);
-    } else if (use_mfma) {
-      ConvPlan pl{co_t, rows_, true};
-      ca.w = (co_t == w.co_t) ? w.packed : w.packed32;
-      ca.kchunk_stages = kchunk; ca.partial = partial;
-      launch_conv_mfma(ca, w.ks, pl, stream_, -1, ksplit);
-      if (partial) arena_.release(partial);
-      if (noting())
-        snprintf(prof_note_, sizeof prof_note_, "conv%dx%d %d->%d @%dx%dx%d tile %dco x %drows%s%s%s%s", w.ks, w.ks, Cin, w.cout, B_, a.H, a.W,
-                 co_t, rows_, res ? " +res" : "", xf.scale ? " +gn" : "", ksplit > 1 ? " split-K" : "", ca.rag_cols ? " existing-tiles" : "");
-      // class "wide" = the dominant kernel family only: the split kernels, or (SGMSE_CONV_SPLIT=0) the fp32 128 x 256 tile
-      tick(w.ks == 3 ? ((split_mode_ == 0 && co_t == 128 && pl.rows == 8) ? TC_CONV3_BIG : TC_CONV3) : TC_CONV1, fl);
-    } else {
-      ca.w = w.oihw;
-      ca.stats_out = nullptr;
-      launch_conv_direct(ca, w.ks, stream_);
-      if (noting()) snprintf(prof_note_, sizeof prof_note_, "conv-direct%dx%d %d->%d @%dx%dx%d", w.ks, w.ks, Cin, w.cout, B_, a.H, a.W);
-      tick(TC_DIRECT, fl);
-      if (o.st) {
-        tock();
-        DRT_LAUNCH(gn_chan_stats_kernel, dim3(B_ * w.cout), dim3(256), stream_, (const float*)o.p, (const float*)nullptr, w.cout, 0,
-                   a.H * a.W, o.st, rag_of(a.H), a.H);
-        if (noting()) snprintf(prof_note_, sizeof prof_note_, "gn_chan_stats(direct) C=%d @%dx%dx%d", w.cout, B_, a.H, a.W);
-        tick(TC_GN, 4.0 * B_ * (double)w.cout * a.H * a.W, 1);
-      }
+        [[fallthrough]];
+      case ConvFamily::Wino23:
+        ca.w = w.packed_wino; ca.co_scale = w.wino_scale; ca.xbound = xf.bound;
+        launch_conv_wino(w.wino_form, ca, stream_, rt.rows4);
+        note_split(fam == ConvFamily::Wino43 ? "wino43" : "wino");
+        break;
+      case ConvFamily::Split:
+      case ConvFamily::SplitCoarse:
+        ca.w = w.packed_split; ca.co_scale = w.split_scale;      // (null for bf16x3: no scale)
+        if (w.ks == 1 && w.split_mode == 2) { ca.amax1 = a.amax; ca.amax2 = b ? b->amax : nullptr; }
+        if (w.ks == 3 && w.split_mode == 2) ca.xbound = xf.bound;
+        launch_conv_split(ca, w.ks, w.split_mode, stream_, rt.rows4, 0, rt.ksplit);
+        note_split("split");
+        break;
+      case ConvFamily::Mfma:
+        ca.w = (rt.co_t == w.co_t) ? w.packed : w.packed32;
+        launch_conv_mfma(ca, w.ks, ConvPlan{rt.co_t, rt.rows, true}, stream_, -1, rt.ksplit);
+        if (noting())
+          snprintf(prof_note_, sizeof prof_note_, "conv%dx%d %d->%d @%dx%dx%d tile %dco x %drows%s%s%s%s", w.ks, w.ks, Cin, w.cout, B_, a.H, a.W,
+                   rt.co_t, rt.rows, rs, gn, rt.ksplit > 1 ? " split-K" : "", ex);
+        // class "wide" = the dominant kernel family only: the split kernels, or (SGMSE_CONV_SPLIT=0) the fp32 128 x 256 tile
+        cls = w.ks == 3 ? ((split_mode_ == 0 && rt.co_t == 128 && rt.rows == 8) ? TC_CONV3_BIG : TC_CONV3) : TC_CONV1;
+        break;
+      case ConvFamily::Direct:
+        ca.w = w.oihw; ca.stats_out = nullptr;
+        launch_conv_direct(ca, w.ks, stream_);
+        if (noting()) snprintf(prof_note_, sizeof prof_note_, "conv-direct%dx%d %d->%d @%dx%dx%d", w.ks, w.ks, Cin, w.cout, B_, a.H, a.W);
+        cls = TC_DIRECT;
+        break;
+    }
+    tick(cls, fl);
+    if (partial) arena_.release(partial);
+    if (fam == ConvFamily::Direct && o.st) {
+      tock();
+      DRT_LAUNCH(gn_chan_stats_kernel, dim3(B_ * w.cout), dim3(256), stream_, (const float*)o.p, (const float*)nullptr, w.cout, 0,
+                 a.H * a.W, o.st, rag_of(a.H), a.H);
+      if (noting()) snprintf(prof_note_, sizeof prof_note_, "gn_chan_stats(direct) C=%d @%dx%dx%d", w.cout, B_, a.H, a.W);
+      tick(TC_GN, 4.0 * B_ * (double)w.cout * a.H * a.W, 1);
     }
     return o;
   }
@@ -1623,7 +1472,7 @@ class Engine {
   void launch_fir(const FirArgs& fa, bool up, bool by_level = false) {
     const int H = fa.H, W = fa.W, BC = fa.BC;
     // tiled or per-pixel kernel: by the LEVEL (dec_W) inside the network, so that an utterance's FIR never depends on its length
-    const bool tiled = by_level ? (W % 4 == 0 && dec_W(H) >= 64 && rag_all_mult4(H)) : fir_use_tiled(W);
+    const bool tiled = by_level ? (W % 4 == 0 && dec_W(H) >= 64 && rag_all_mult(H, 4)) : fir_use_tiled(W);
     if (tiled && !fir_scalar_) {
       if (up) DRT_LAUNCH(fir_up2_tiled_kernel, dim3(((W + 63) / 64) * ((H + 7) / 8), BC), dim3(256), stream_, fa);
       else DRT_LAUNCH(fir_down2_tiled_kernel, dim3(((W / 2 + 63) / 64) * ((H / 2 + 7) / 8), BC), dim3(256), stream_, fa);
@@ -1663,9 +1512,13 @@ class Engine {
     // below the split kernels' threshold, and any layer the fold's conditions exclude): it needs the block input only and its result only
     // at the end of the block, so at small batches it runs on the side stream beside GroupNorm - Conv_0 - GroupNorm (round 6).
     Tensor sh_t; bool sc_side = false;
-    auto shortcut_early = [&](const Tensor& sa, const Tensor* sb, int Ch, int Hh) {
+    // Does Conv_1's launch take the shortcut?  Asked of Conv_1's own route (it reads the Conv_0 output, the shortcut input's shape, behind
+    // GroupNorm_1 + SiLU with a known bound), once per block: the early launch below and the Conv_1 call cannot disagree.
+    bool fold = false;
+    auto shortcut_early = [&](const Tensor& sa, const Tensor* sb) {
       if (!r.has_c2) return;
-      const bool fold = runs_on_h2_split3(r.c1, Ch, Hh, dec_W(Hh)) && shortcut_foldable(r.c2, sa, sb) && !((nofold_levels_ >> level_of(Hh)) & 1) && !runs_on_wino43(r.c1, Hh);
+      fold = route_of(r.c1, r.c0.cout, 0, sa.H, sa.W, ConvCall{true, true, true, true, false, true}).accepts_shortcut &&
+             shortcut_foldable(r.c2, sa, sb) && !((nofold_levels_ >> level_of(sa.H)) & 1);
       if (fold || !side_enabled()) return;
       side_begin();
       sh_t = conv(r.c2, sa, sb, Xform{}, r.c2.bias, nullptr, nullptr, 1.f, ctl);
@@ -1676,11 +1529,11 @@ class Engine {
       SG_REQUIRE(b == nullptr, "resample block with concat input");
       Tensor hr = fir(a, m.up, x0, &xs);
       have_xs = true;
-      shortcut_early(xs, nullptr, r.c0.cout, hr.H);
+      shortcut_early(xs, nullptr);
       h = conv(r.c0, hr, nullptr, Xform{nullptr, nullptr, 0, bd0}, nullptr, temb, nullptr, 1.f, ctl, true);
       drop(hr);
     } else {
-      shortcut_early(a, b, r.c0.cout, a.H);
+      shortcut_early(a, b);
       h = conv(r.c0, a, b, x0, nullptr, temb, nullptr, 1.f, ctl, true);
     }
     arena_.release(sc0); arena_.release(sh0);
@@ -1691,7 +1544,7 @@ class Engine {
     if (r.has_c2) {
       const Tensor& sa = have_xs ? xs : a;
       const Tensor* sb = have_xs ? nullptr : b;
-      if (runs_on_h2_split3(r.c1, h.C, h.H, dec_W(h.H)) && shortcut_foldable(r.c2, sa, sb) && !((nofold_levels_ >> level_of(h.H)) & 1) && !runs_on_wino43(r.c1, h.H)) {
+      if (fold) {
         // (Conv_1(h) + Conv_2(x)) / sqrt 2 as one accumulation: the shortcut's K-stages run inside the 3x3 launch
         const Shortcut scin{&r.c2, &sa, sb};
         out = conv(r.c1, h, nullptr, x1, r.c1.bias, nullptr, nullptr, inv_sqrt2, ctl, true, &scin);
@@ -2015,7 +1868,6 @@ class Engine {
 
   Arena arena_; char* arena_base_ = nullptr; size_t arena_cap_ = 0;
   bool dry_ = false;
-  // measurement knobs, re-read from the environment at every configure (so one process can compare settings)
   // Runtime switches, re-read from the environment at every configure / weight load (so one process can compare settings).
   // User-facing: SGMSE_CONV_SPLIT, SGMSE_WINO, SGMSE_WINO43, SGMSE_CONV_XCD_MAP, SGMSE_RAGGED_PREFIX, SGMSE_DEBUG_SYNC,
   // SGMSE_PROFILE_DUMP.  Test hooks (what the bitwise / parity tests toggle to reach a code path; not for users):

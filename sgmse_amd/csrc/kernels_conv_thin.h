@@ -34,9 +34,7 @@ struct ConvThinGeom {
   static constexpr int NI = (NPOS + 255) / 256;                 // per thread and channel
 };
 
-inline bool conv_thin_eligible(int ks, int C1, int C2, int Cout) {
-  return ks == 3 && Cout <= 4 && (C1 + C2) % ConvThinGeom::KC == 0 && (C2 == 0 || C1 % ConvThinGeom::KC == 0) && (C1 + C2) <= 512;
-}
+// (conv_thin_eligible: conv_route.h)
 inline size_t packed_thin_elems(int Cin) { return (size_t)Cin * 36; }
 // OIHW -> [ci][tap][4 co] (output channels beyond Cout are zero)
 __global__ void pack_weights_thin_kernel(const float* __restrict__ oihw, float* __restrict__ dst, int Cin, int Cout) {
