@@ -118,6 +118,19 @@ inline void launch_conv3x3_split_t(const ConvArgs& a, dim3 grid, drt::stream_t s
   if (act) DRT_LAUNCH((conv3x3_split_kernel<S, SHAPE, 1>), grid, dim3(256), st, a);
   else DRT_LAUNCH((conv3x3_split_kernel<S, SHAPE, 0>), grid, dim3(256), st, a);
 }
+// 1x1: a launch without a producer (every residual shortcut) runs the raw-input instantiation, with 16-byte staging loads where every
+// width of the launch is a multiple of 4 and the sources are 16-byte aligned; the instantiations give the same bits
+#ifndef SGMSE_CONV1X1_RAW_VEC
+#define SGMSE_CONV1X1_RAW_VEC 1        // 0: measurement builds, raw-input instantiation with the 4-byte staging everywhere
+#endif
+template <class S>
+inline void launch_conv1x1_split_t(const ConvArgs& a, dim3 grid, drt::stream_t st) {
+  if (a.in_scale) { DRT_LAUNCH((conv1x1_split_kernel<S, 1, 0>), grid, dim3(256), st, a); return; }
+  const bool vec = SGMSE_CONV1X1_RAW_VEC && (a.rag_w ? a.rag_vec_ok != 0 : a.W % 4 == 0) && reinterpret_cast<uintptr_t>(a.src1) % 16 == 0 &&
+                   (a.src2 == nullptr || reinterpret_cast<uintptr_t>(a.src2) % 16 == 0);
+  if (vec) DRT_LAUNCH((conv1x1_split_kernel<S, 0, 1>), grid, dim3(256), st, a);
+  else DRT_LAUNCH((conv1x1_split_kernel<S, 0, 0>), grid, dim3(256), st, a);
+}
 inline void launch_conv_split(const ConvArgs& a, int ks, int mode, drt::stream_t st, bool rows4 = false, int abl = 0, int ksplit = 1) {
   const int tiles = conv_grid_tiles(a, 8);
   if (ks == 3 && a.Cout > 32 && rows4 && a.kchunk_stages > 0 && mode == 2) {     // chunked accumulation / split-K (coarse levels)
@@ -137,8 +150,8 @@ inline void launch_conv_split(const ConvArgs& a, int ks, int mode, drt::stream_t
     return;
   }
   if (ks == 1) {
-    if (mode == 2) DRT_LAUNCH(conv1x1_split_kernel<SplitH2>, dim3(tiles, a.Cout / 128, 1), dim3(256), st, a);
-    else DRT_LAUNCH(conv1x1_split_kernel<SplitB3>, dim3(tiles, a.Cout / 128, 1), dim3(256), st, a);
+    if (mode == 2) launch_conv1x1_split_t<SplitH2>(a, dim3(tiles, a.Cout / 128, 1), st);
+    else launch_conv1x1_split_t<SplitB3>(a, dim3(tiles, a.Cout / 128, 1), st);
     return;
   }
   const dim3 grid(tiles, a.Cout / 128, 1);

@@ -611,11 +611,13 @@ class Engine {
       a.w = pk;
       float *bounds = nullptr, *xb = nullptr;
       if (smode == 2) {      // dynamic input scale: range bounds as the producers would have left them
-        SG_REQUIRE(ks == 3 || in_scale == nullptr, "op_conv2d: the fp16x2 1x1 kernel takes raw inputs (no fused producer)");
         bounds = input_bounds(x, a.C1, x2, C2, B, H * W);
         const float* am2 = x2 ? bounds + (size_t)B * kAmaxSpread : nullptr;
-        if (ks == 1) { a.amax1 = bounds; a.amax2 = am2; }
-        else { xb = producer_bound(in_scale, in_shift, Cin, bounds, am2, B); a.xbound = xb; }
+        if (ks == 1 && in_scale == nullptr) { a.amax1 = bounds; a.amax2 = am2; }      // raw input, as the network's shortcuts run it
+        else {      // a fused producer: the kernel scales by the bound of the producer's output (1x1: in the place of the raw range)
+          xb = producer_bound(in_scale, in_shift, Cin, bounds, am2, B);
+          if (ks == 1) a.amax1 = xb; else a.xbound = xb;
+        }
       }
       if (wino) launch_conv_wino(form, a, stream_, force_direct == FC_WINO_4ROW || force_direct == FC_WINO43_4ROW);
       else launch_conv_split(a, ks, smode, stream_);

@@ -719,16 +719,26 @@ __global__ __launch_bounds__(256, 2) void conv3x3_split_kernel(ConvArgs p) {
 // s+1 is spread over the pixel fragments of stage s.  Inputs of these layers are raw residual-stream activations of
 // unknown range: bf16x3 needs no range; fp16x2 scales by an exact power of two derived per utterance from the range
 // bounds the producing kernels left behind (ConvArgs::amax1/amax2), so that max|x| 2^s lies in [2^13, 2^14).
-template <class S>
+// XF (chosen by the host from ConvArgs::in_scale): 1 = a fused producer (per-channel affine, optional SiLU; the attention NIN and
+//   the coarse levels under bf16x3).  0 = raw input, which is every residual shortcut of the network: no coefficient tables, no
+//   affine, no exp / rcp / blend, and no barrier that only publishes the tables -- what is left per element is the scale by xs, the
+//   clamp and the split.  x * 1 + 0 is x for every non-zero x, so XF = 0 gives the bits of XF = 1 with the identity producer.
+// VEC (XF = 0 only; host: every width of the launch a multiple of 4, sources 16-byte aligned): a staging item is (k-group, channel
+//   half, row, aligned column quad) -- 256 items, one per thread, FOUR 16-byte loads per thread and stage where the 4-byte staging
+//   issues sixteen; the thread converts 4 channels x 4 pixels and writes the 8-byte halves of the same [pixel][k-group][split] LDS
+//   entries.  A quad lies wholly inside or wholly outside the image (outside: clamped, never stored).  Same operands, same LDS
+//   contents, same MFMA order: no result bit depends on XF = 0 / VEC.
+template <class S, int XF = 1, int VEC = 0>
 __global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(ConvArgs p) {
   using T = ConvTile<1, 4, 1, 8, 1>;
   static_assert(T::CO_T == 128 && T::ROWS == 8, "tile");
+  static_assert(!VEC || !XF, "16-byte staging exists for raw inputs only");
   constexpr int NS = S::NS, PX_V = S::PX_V, KC = 16, NIT = 2;     // 256 px x 2 k-groups = 512 items = 2 per thread
   constexpr int STAGE_V = 256 * PX_V;
   __shared__ u32x4 s_in0[STAGE_V];
   __shared__ u32x4 s_in1[STAGE_V];
-  __shared__ float s_sc[512];
-  __shared__ float s_sh[512];
+  __shared__ float s_sc[XF ? 512 : 1];
+  __shared__ float s_sh[XF ? 512 : 1];
 
   const int tid = threadIdx.x;
   const int Cin = p.C1 + p.C2;
@@ -741,12 +751,15 @@ __global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(ConvArgs p) {
   const int tiles_x = (W + 31) >> 5;
   const int co_blk = blockIdx.y;
   const int x0 = tx * 32, y0 = ty * 8;
-  const bool xform = p.in_scale != nullptr;
-  for (int c = tid; c < Cin; c += 256) {
-    s_sc[c] = xform ? p.in_scale[b * Cin + c] : 1.f;
-    s_sh[c] = xform ? p.in_shift[b * Cin + c] : 0.f;
+  float actf = 0.f;
+  if constexpr (XF) {
+    const bool xform = p.in_scale != nullptr;
+    for (int c = tid; c < Cin; c += 256) {
+      s_sc[c] = xform ? p.in_scale[b * Cin + c] : 1.f;
+      s_sh[c] = xform ? p.in_shift[b * Cin + c] : 0.f;
+    }
+    actf = (xform && p.in_act) ? 1.f : 0.f;
   }
-  const float actf = (xform && p.in_act) ? 1.f : 0.f;
   const size_t HW = (size_t)H * W;
   const int wave = tid >> 6, lane = tid & 63, l31 = lane & 31, kg = lane >> 5;
   // fp16x2 on a raw (residual-stream) input: exact power-of-two scale from the producers' per-utterance range bounds, so
@@ -760,33 +773,58 @@ __global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(ConvArgs p) {
 
   // staging items: (k-group g, row r, column c), c fastest; pixels outside the image are clamped (their outputs are
   // never stored and a 1x1 convolution does not mix pixels)
+  // VEC: ONE item (k-group g, channel half h, row r, column quad cq), cq fastest: channels 8 g + 4 h .. + 3 of the four pixels
+  // (r, 4 cq .. 4 cq + 3); it_goff[0] / it_loff[0] / it_g[0] = its pixel offset, its LDS offset in 8-byte units, its first channel
   int it_goff[NIT], it_loff[NIT], it_g[NIT];
+  if constexpr (VEC) {
+    const int cq = tid & 7, h = (tid >> 3) & 1, g = (tid >> 4) & 1, r = tid >> 5;
+    int gy = y0 + r, gx = x0 + 4 * cq;
+    gy = gy < H ? gy : H - 1; gx = gx < W ? gx : W - 4;           // (W % 4 == 0: the quad is inside, or it starts at or beyond W)
+    it_goff[0] = gy * W + gx;
+    it_loff[0] = ((r * 32 + 4 * cq) * PX_V + g * NS) * 2 + h;
+    it_g[0] = 8 * g + 4 * h;
+    it_goff[1] = it_loff[1] = it_g[1] = 0;
+  } else {
 #pragma unroll
-  for (int i = 0; i < NIT; ++i) {
-    const int it = tid + 256 * i;
-    const int g = it >> 8, r = (it >> 5) & 7, c = it & 31;
-    int gy = y0 + r, gx = x0 + c;
-    gy = gy < H ? gy : H - 1; gx = gx < W ? gx : W - 1;
-    it_goff[i] = gy * W + gx;
-    it_loff[i] = (r * 32 + c) * PX_V + g * NS;
-    it_g[i] = g;
+    for (int i = 0; i < NIT; ++i) {
+      const int it = tid + 256 * i;
+      const int g = it >> 8, r = (it >> 5) & 7, c = it & 31;
+      int gy = y0 + r, gx = x0 + c;
+      gy = gy < H ? gy : H - 1; gx = gx < W ? gx : W - 1;
+      it_goff[i] = gy * W + gx;
+      it_loff[i] = (r * 32 + c) * PX_V + g * NS;
+      it_g[i] = g;
+    }
   }
+  // raw values of one stage: [item][element] = channel 8 g + e of the item's pixel; VEC: [e >> 1][4 (e & 1) + q] = channel e of pixel q
   float rinA[NIT][8], rinB[NIT][8];
   auto load_items = [&](int c0, float (&dst)[NIT][8]) {
     const bool first = c0 < p.C1;
     const float* base = first ? p.src1 + ((size_t)b * p.C1 + c0) * HW : p.src2 + ((size_t)b * p.C2 + (c0 - p.C1)) * HW;
+    if constexpr (VEC) {
 #pragma unroll
-    for (int i = 0; i < NIT; ++i)
+      for (int e = 0; e < 4; ++e) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(base + (size_t)(it_g[0] + e) * HW + it_goff[0]);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) dst[i][e] = base[(size_t)(8 * it_g[i] + e) * HW + it_goff[i]];
+        for (int q = 0; q < 4; ++q) dst[e >> 1][4 * (e & 1) + q] = v[q];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NIT; ++i)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dst[i][e] = base[(size_t)(8 * it_g[i] + e) * HW + it_goff[i]];
+    }
   };
   u32x4 pk[NS];
   uint32_t ev[NS];
   auto stage_elem = [&](int i, int e, int c0, const float (&src)[NIT][8]) {
-    const int ch = c0 + 8 * it_g[i] + e;
-    float t = src[i][e] * s_sc[ch] + s_sh[ch];
-    const float sig = __builtin_amdgcn_rcpf(1.0f + __expf(-t));
-    t *= actf * (sig - 1.0f) + 1.0f;
+    float t = src[i][e];
+    if constexpr (XF) {
+      const int ch = c0 + 8 * it_g[i] + e;
+      t = t * s_sc[ch] + s_sh[ch];
+      const float sig = __builtin_amdgcn_rcpf(1.0f + __expf(-t));
+      t *= actf * (sig - 1.0f) + 1.0f;
+    }
     if (S::SCALED) t = fminf(fmaxf(t * xs, -65504.f), 65504.f);    // the clamp cannot bind when the range bound holds
     uint32_t t16[NS];
     S::split(t, t16);
@@ -798,6 +836,25 @@ __global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(ConvArgs p) {
   auto flush_item = [&](int i, u32x4* sbuf) {
 #pragma unroll
     for (int s = 0; s < NS; ++s) sbuf[it_loff[i] + s] = pk[s];
+  };
+  // VEC: step k of 8 = pixel q = k / 2 of the quad, channel pair k % 2 (S::split2: the bits of S::split on either element); the
+  // second pair completes the pixel's 8-byte half entries
+  uint32_t hv[NS];
+  auto stage_quad = [&](int k, const float (&src)[NIT][8], u32x4* sbuf) {
+    const int q = k >> 1, cp = k & 1;
+    float t0 = src[cp][q], t1 = src[cp][4 + q];
+    if (S::SCALED) { t0 = fminf(fmaxf(t0 * xs, -65504.f), 65504.f); t1 = fminf(fmaxf(t1 * xs, -65504.f), 65504.f); }
+    uint32_t d[NS];
+    S::split2(t0, t1, d);
+    if (cp == 0) {
+#pragma unroll
+      for (int s = 0; s < NS; ++s) hv[s] = d[s];
+    } else {
+      typedef unsigned long long __attribute__((may_alias)) u64a;          // (8-byte stores into the u32x4 stage buffer)
+      u64a* q8 = reinterpret_cast<u64a*>(sbuf) + it_loff[0] + q * PX_V * 2;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) q8[2 * s] = (unsigned long long)hv[s] | ((unsigned long long)d[s] << 32);
+    }
   };
 
   f32x16 acc[1][8];
@@ -817,12 +874,17 @@ __global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(ConvArgs p) {
 
   // prologue: stage 0 -> LDS, stage 1 -> rinA
   load_items(0, rinA);
-  __syncthreads();
+  if constexpr (XF) __syncthreads();               // (publishes s_sc / s_sh)
+  if constexpr (VEC) {
 #pragma unroll
-  for (int i = 0; i < NIT; ++i) {
+    for (int k = 0; k < 8; ++k) stage_quad(k, rinA, s_in0);
+  } else {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) stage_elem(i, e, 0, rinA);
-    flush_item(i, s_in0);
+    for (int i = 0; i < NIT; ++i) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) stage_elem(i, e, 0, rinA);
+      flush_item(i, s_in0);
+    }
   }
   load_items((nst > 1 ? 1 : 0) * KC, rinA);
   u32x4 a0[NS], a1[NS];
@@ -853,10 +915,14 @@ __global__ __launch_bounds__(256, 2) void conv1x1_split_kernel(ConvArgs p) {
 #pragma unroll
       for (int k = 0; k < S::NP; ++k) c = S::mfma(a0[S::pa(k)], bq[j & 1][S::pb(k)], c);
       acc[0][j] = c;
-      // stage st+1 (raw values in rinA): item j / 4, elements 2 (j % 4) and 2 (j % 4) + 1
-      stage_elem(j >> 2, 2 * (j & 3), st1 * KC, rinA);
-      stage_elem(j >> 2, 2 * (j & 3) + 1, st1 * KC, rinA);
-      if ((j & 3) == 3) flush_item(j >> 2, nxt);
+      if constexpr (VEC) {
+        stage_quad(j, rinA, nxt);       // stage st+1 (raw values in rinA): pixel j / 2 of the quad, channel pair j % 2
+      } else {
+        // stage st+1 (raw values in rinA): item j / 4, elements 2 (j % 4) and 2 (j % 4) + 1
+        stage_elem(j >> 2, 2 * (j & 3), st1 * KC, rinA);
+        stage_elem(j >> 2, 2 * (j & 3) + 1, st1 * KC, rinA);
+        if ((j & 3) == 3) flush_item(j >> 2, nxt);
+      }
       __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();

@@ -27,6 +27,7 @@ ALL_SHAPES = [  # ks, B, Cin, Cout, H, W
     (3, 32, 128, 128, 256, 512),
     (3, 128, 128, 128, 64, 128),
     (3, 2, 128, 128, 256, 512),
+    (1, 8, 128, 128, 256, 512),      # the 128-channel residual shortcut beside shape 3 (256 -> 128): the two 1x1 shapes of the wide levels
 ]
 SHAPES = [ALL_SHAPES[int(i)] for i in os.environ.get("SHAPES", "0,1,2,3").split(",")]
 FUSED = [int(v) for v in os.environ.get("FUSED", "0,1").split(",")]
