@@ -109,6 +109,35 @@ int sgmse_sb_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int 
                     const float* w_est, const float* w_y, const float* w_z, const float* in_scale, const float* score_alpha,
                     const float* score_beta, int stochastic, const void* noise, unsigned long long seed, int use_graph, int* nfe);
 
+/* -- get_ode_sampler(sde, score_fn, y, denoise=False, rtol, atol, method="RK45")() (sampling/__init__.py:96-143) with the solver in
+ *    the library: Dormand-Prince 5(4) with the step control of scipy's RK45 (initial step, error norm over the WHOLE flattened batch,
+ *    accept / reject factors, minimum step 10 ulp(t), last step clipped to eps) over the OUVE probability-flow drift
+ *    theta (y - x) - g(t)^2 score / 2, from t_end (sde.T) down to eps.  State, stage slopes and error estimate stay on the device;
+ *    one scalar per attempted step (the error norm) reaches the host, where the step control runs in double.
+ *    Y, out: complex64 [B][1][F][T].  Prior: x0 (complex64 like Y: the start state itself), else y + std1 * z with z = noise
+ *    (complex64 like Y, replayed) or the Philox stream of `seed` and the noise-stream ids.  *nfe receives the evaluation count,
+ *    counted as scipy's nfev (1 + 1 for the automatic first step + 6 per attempted step).
+ *    Errors (SGMSE_ERUNTIME, message in the last-error string): more than max_nfe evaluations needed; step size below 10 ulp(t) (a
+ *    non-finite error norm counts as a rejected step and ends there); a ragged context (the error norm couples the utterances).
+ *    coef_fn (may be NULL = old-code score wrapper, score = -F): the score wrapper of ncsnpp_v2 models at times only the solver
+ *    knows; called on the host once per attempted step with that attempt's n stage times (fp32, as the network sees them), fills
+ *    in_scale (gamma), score_alpha, score_beta [n] as in the sampler configuration above. */
+typedef void (*sgmse_ode_coef_fn)(void* user, int n, const float* t, float* gamma, float* alpha, float* beta);
+typedef struct sgmse_ode_cfg {
+  float theta, sigma_min, sigma_max;   /* OUVESDE */
+  float std1;                          /* OUVESDE._std(T) for the prior draw (unused with x0) */
+  double t_end, eps;                   /* integrate from t_end = sde.T to eps */
+  double rtol, atol;
+  double first_step, max_step;         /* 0: scipy's select_initial_step / no limit */
+  int max_nfe;                         /* cap on evaluations */
+  sgmse_ode_coef_fn coef_fn; void* coef_user;
+} sgmse_ode_cfg;
+int sgmse_ode_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int T, const sgmse_ode_cfg* cfg, const void* noise,
+                     const void* x0, unsigned long long seed, int* nfe);
+/* the last sgmse_ode_sample run of this context: accepted and rejected step counts and the first min(cap, accepted) accepted time
+ * points (the last one is eps exactly after a completed run).  Any of the pointers may be NULL. */
+int sgmse_ode_stats(sgmse_ctx* ctx, int* accepted, int* rejected, double* t_accepted, int cap);
+
 /* -- SpecsDataModule.stft / istft / spec_fwd / spec_back (data_module.py:162-188,212-218) ---------------------
  * sig fp32 [B][L] -> spec complex64 [B][n_fft/2+1][L/hop+1] (center=True, reflect pad, window fp32 [n_fft]). */
 int sgmse_stft(sgmse_ctx* ctx, const float* sig, const float* window, void* spec, int B, int L, int n_fft, int hop);

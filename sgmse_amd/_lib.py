@@ -39,6 +39,16 @@ class SamplerCfgC(C.Structure):
                 ("snr", C.c_float), ("use_graph", C.c_int)]
 
 
+ODE_COEF_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float))
+
+
+class OdeCfgC(C.Structure):
+    _fields_ = [("theta", C.c_float), ("sigma_min", C.c_float), ("sigma_max", C.c_float), ("std1", C.c_float),
+                ("t_end", C.c_double), ("eps", C.c_double), ("rtol", C.c_double), ("atol", C.c_double),
+                ("first_step", C.c_double), ("max_step", C.c_double), ("max_nfe", C.c_int), ("coef_fn", ODE_COEF_FN),
+                ("coef_user", C.c_void_p)]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _F = C.c_float
@@ -56,6 +66,8 @@ _SIGS = {
     "sgmse_ncsnpp_forward": (_I, [_P, _P, _P, _P, _I, _I, _I]),
     "sgmse_pc_sample": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(SamplerCfgC), _P, C.c_ulonglong, C.POINTER(_I)]),
     "sgmse_sb_sample": (_I, [_P, _P, _P, _I, _I, _I, _I] + [C.POINTER(_F)] * 8 + [_I, _P, C.c_ulonglong, _I, C.POINTER(_I)]),
+    "sgmse_ode_sample": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(OdeCfgC), _P, _P, C.c_ulonglong, C.POINTER(_I)]),
+    "sgmse_ode_stats": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_double), _I]),
     "sgmse_stft": (_I, [_P, _P, _P, _P, _I, _I, _I, _I]),
     "sgmse_istft": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "sgmse_spec_fwd": (_I, [_P, _P, _P, _LL, _I, _F, _F]),
@@ -388,6 +400,78 @@ class Context:
             run()
         self._keep["sb"] = (noise, keep, aff)
         return out, nfe.value
+
+    def ode_sample(self, Y: torch.Tensor, *, theta: float, sigma_min: float, sigma_max: float, std1: float, t_end: float, eps: float,
+                   rtol: float, atol: float, first_step: float = 0.0, max_step: float = 0.0, noise: Optional[torch.Tensor] = None,
+                   x0: Optional[torch.Tensor] = None, seed: int = 0, streams=None, affine_fn=None, max_nfe: int = 100000):
+        """Adaptive probability-flow sampler inside the library (sgmse_ode_sample): Dormand-Prince 5(4) with scipy's RK45 step
+        control, state and stage slopes on the device.  ``x0``: the start state itself; else the prior y + std1 z with ``noise``
+        ([B,1,F,T], or the samplers' [ndraws,B,1,F,T] layout whose first entry is the prior draw) or the Philox stream of
+        (``seed``, ``streams``).  ``affine_fn``: ``ScoreModel.score_affine`` of an ncsnpp_v2 model (None: old-code wrapper), called
+        with each attempted step's stage times.  Returns (sample, nfe); ``ode_stats`` describes the run.  Raises RuntimeError when
+        the solver needs more than ``max_nfe`` evaluations or its step size underflows."""
+        if isinstance(Y, (list, tuple)):
+            raise TypeError("the adaptive ODE sampler integrates one rectangular batch (its error norm couples the utterances): "
+                            "pass a tensor, not a ragged list")
+        Y = check_tensor(Y, "y", torch.complex64, self.device)
+        if Y.dim() != 4 or Y.shape[1] != 1:
+            raise ValueError(f"expected y of shape [B,1,F,T], got {tuple(Y.shape)}")
+        B, _, F_, T = Y.shape
+        if noise is not None and x0 is not None:
+            raise ValueError("give replayed noise or a start state, not both")
+        if noise is not None:
+            noise = check_tensor(noise, "noise", torch.complex64, self.device)
+            if noise.dim() == Y.dim() + 1:
+                noise = noise[0].contiguous()
+            if tuple(noise.shape) != tuple(Y.shape):
+                raise ValueError(f"noise must be [{B},1,{F_},{T}] complex64 (or [ndraws,{B},1,{F_},{T}]), got {tuple(noise.shape)}")
+        if x0 is not None:
+            x0 = check_tensor(x0, "z", torch.complex64, self.device)
+            if tuple(x0.shape) != tuple(Y.shape):
+                raise ValueError(f"the start state must have y's shape {tuple(Y.shape)}, got {tuple(x0.shape)}")
+        cfg = OdeCfgC()
+        cfg.theta, cfg.sigma_min, cfg.sigma_max, cfg.std1 = float(theta), float(sigma_min), float(sigma_max), float(std1)
+        cfg.t_end, cfg.eps, cfg.rtol, cfg.atol = float(t_end), float(eps), float(rtol), float(atol)
+        cfg.first_step, cfg.max_step, cfg.max_nfe = float(first_step), float(max_step), int(max_nfe)
+        failure = []
+        if affine_fn is not None:
+            def _coef(user, n, t, gamma, alpha, beta):      # host callback: exceptions must not cross the C frames
+                try:
+                    rows = affine_fn(torch.tensor([t[i] for i in range(n)], dtype=torch.float32))
+                    for dst, v in zip((gamma, alpha, beta), rows):
+                        v = torch.as_tensor(v, dtype=torch.float32).reshape(-1).expand(n)
+                        for i in range(n):
+                            dst[i] = float(v[i])
+                except Exception as e:      # noqa: BLE001
+                    failure.append(e)
+                    for i in range(n):
+                        gamma[i] = alpha[i] = beta[i] = float("nan")
+            cb = ODE_COEF_FN(_coef)
+            cfg.coef_fn = cb
+        if streams is not None:
+            if len(streams) != B:
+                raise ValueError(f"streams must name the {B} utterances of the batch, got {len(streams)}")
+            self.set_noise_streams(streams)
+        out = torch.empty_like(Y)
+        nfe = _I(0)
+        self.use_current_stream()
+        # as in forward / pc_sample / sb_sample: a frame table left in force by an earlier ragged call is no request of this caller's
+        # (a ragged batch is a list, refused above); a uniform call switches it off
+        self.set_frames([])
+        rc = self.lib.sgmse_ode_sample(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, C.byref(cfg), ptr(noise), ptr(x0),
+                                       C.c_ulonglong(seed & (2 ** 64 - 1)), C.byref(nfe))
+        if failure:
+            raise failure[0]
+        self.check(rc)
+        return out, nfe.value
+
+    def ode_stats(self):
+        """The last ``ode_sample`` run: dict(accepted=..., rejected=..., t=[accepted time points])."""
+        acc, rej = _I(0), _I(0)
+        self.check(self.lib.sgmse_ode_stats(self.h, C.byref(acc), C.byref(rej), None, 0))
+        ts = (C.c_double * max(acc.value, 1))()
+        self.check(self.lib.sgmse_ode_stats(self.h, C.byref(acc), C.byref(rej), ts, acc.value))
+        return dict(accepted=acc.value, rejected=rej.value, t=[ts[i] for i in range(acc.value)])
 
     def profile_forward(self, xy, t: torch.Tensor):
         """Per-kernel-class HIP-event timing of ONE network evaluation (eager).  xy: complex64 [B,2,F,T], or a list of [2,F,T_b]

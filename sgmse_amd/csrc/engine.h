@@ -19,6 +19,7 @@
 #include "conv_launch.h"
 #include "kernels_norm_fir.h"
 #include "kernels_attn_misc.h"
+#include "kernels_ode.h"
 #include "kernels_stft.h"
 
 namespace sgmse {
@@ -317,6 +318,20 @@ struct SamplerCfg {
   int use_graph = 1;
 };
 
+// Engine::ode_sample (adaptive probability-flow sampler, kernels_ode.h)
+struct OdeCfg {
+  float theta = 1.5f, sigma_min = 0.05f, sigma_max = 0.5f;
+  float std1 = 0.f;                       // OUVE._std(T) for the prior draw
+  double t_end = 1.0, eps = 0.03;          // integrate from t_end (sde.T) to eps
+  double rtol = 1e-5, atol = 1e-5;
+  double first_step = 0.0, max_step = 0.0; // 0: select_initial_step / no limit
+  int max_nfe = 100000;                    // more evaluations than this is an error
+  // score wrapper of ncsnpp_v2 models at the solver's stage times (null: old-code branch, score = -F): called once per attempted
+  // step with that attempt's n stage times (fp32, as the network sees them); fills gamma / alpha / beta [n]
+  void (*coef_fn)(void* user, int n, const float* t, float* gamma, float* alpha, float* beta) = nullptr;
+  void* coef_user = nullptr;
+};
+
 class Engine {
  public:
   explicit Engine(int device, void* stream) : device_(device) {
@@ -329,6 +344,7 @@ class Engine {
     for (void* p : wowned_) drt::free_dev(p);
     if (graph_valid_ || graph_stale_) drt::graph_destroy(&graph_);
     if (hstage_) drt::free_host(hstage_);
+    if (ode_host_) drt::free_host(ode_host_);
     if (hstage_ev_init_) drt::event_destroy(&hstage_ev_);
     for (drt::event_t& e : side_ev_) drt::event_destroy(&e);
     if (side_stream_ready_) drt::stream_destroy(side_stream_);
@@ -547,6 +563,219 @@ class Engine {
     }
     SG_CHECK(drt::memcpy_d2d(out, sx_, n * 8, stream_));
     nfe_ = N;
+  }
+  // get_ode_sampler(..., denoise=False)() (sampling/__init__.py:96-143) with the solver inside the library: scipy's RK45
+  // (Dormand-Prince 5(4), scipy/integrate/_ivp/rk.py) and its step control (common.py select_initial_step, RungeKutta._step_impl)
+  // over the flattened batch -- ONE error norm for all B*F*T complex elements, as scipy sees the state, so the utterances of a batch
+  // are coupled exactly as in the reference.  State, slopes and error estimate stay on the device (kernels_ode.h); the host runs the
+  // step control in double and reads one scalar, the error norm, per attempted step.  The evaluation count is scipy's nfev.
+  // Prior: x0 (given start state), else y + std1 z with z = noise (replayed, [B][F][T]) or the Philox stream of (seed, streams).
+  void ode_sample(const float2* Y, float2* out, int B, int F, int T, const OdeCfg& oc, const float2* noise, const float2* x0,
+                  unsigned long long seed) {
+    require_ready();
+    SG_REQUIRE(!ragged(), "ode_sample: ragged batches are not supported: the solver's error norm couples the utterances of a batch "
+                          "(call sgmse_set_frames with n = 0 and pass a rectangular batch)");
+    // (rtol, atol, first_step, max_step, max_nfe: checked once, at the C boundary, sgmse_ode_sample)
+    SG_REQUIRE(oc.t_end != oc.eps && oc.eps > 0 && oc.t_end > 0, "ode_sample: bad time span");
+    SG_REQUIRE(oc.sigma_min > 0 && oc.sigma_max > oc.sigma_min, "ode_sample: bad sigma range");
+    const double interval = std::fabs(oc.eps - oc.t_end), dir = oc.eps < oc.t_end ? -1.0 : 1.0;
+    SG_REQUIRE(oc.first_step <= interval, "ode_sample: `first_step` exceeds bounds");
+    ensure_shape(B, F, T, ODE_ROWS);
+    const size_t n = (size_t)B * F * T;
+    if (n > ode_n_) {
+      for (float2** q : {&ode_k_[0], &ode_k_[1], &ode_k_[2], &ode_k_[3], &ode_k_[4], &ode_k_[5], &ode_k_[6], &ode_xs_}) {
+        if (*q) dev_free_owned(*q);
+        *q = static_cast<float2*>(dev_alloc(n * 8));
+      }
+      ode_n_ = n;
+    }
+    if (!ode_table_) {
+      ode_table_ = static_cast<double*>(dev_alloc(sizeof(double) * ODE_ROWS * ODE_STRIDE));
+      ode_partial_ = static_cast<double*>(dev_alloc(sizeof(double) * ODE_NBLK * ODE_NSUM));
+      ode_result_ = static_cast<double*>(dev_alloc(sizeof(double) * ODE_NSUM));
+      SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&ode_host_), sizeof(double) * ODE_NSUM));
+    }
+    ode_accepted_ = ode_rejected_ = 0; ode_t_acc_.clear(); nfe_ = 0;
+
+    // prior
+    const std::vector<float> one_row(SC_STRIDE, 0.f), one_t(1, (float)oc.t_end);
+    const unsigned long long* seed_dev = upload_tables(one_row, one_t, std::vector<float>(), seed, B);    // (also consumes the noise-stream ids)
+    SG_CHECK(drt::memcpy_d2d(sy_, Y, n * 8, stream_));
+    if (x0) {
+      SG_CHECK(drt::memcpy_d2d(sx_, x0, n * 8, stream_));
+    } else {
+      SamplerArgs sa{};
+      sa.x = sx_; sa.y = sy_; sa.noise = noise; sa.seed = seed_dev; sa.std1 = oc.std1; sa.n = (int)n; sa.B = B; sa.per = F * T;
+      DRT_LAUNCH(sampler_prior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), stream_, sa);
+    }
+
+    float2 *xcur = sx_, *xnew = sxm_;
+    float2* K[7];
+    for (int j = 0; j < 7; ++j) K[j] = ode_k_[j];
+    FwdCtl ctl{bias_table_, 0, tot_temb_, step_ctr_, tsteps_, 0, 1, -1.0f};
+    if (oc.coef_fn) { ctl.coef = coef_table_; ctl.coef_bstride = 0; ctl.coef_sstride = 1; }
+    const long long FT = (long long)F * T;
+    const unsigned egrid = (unsigned)std::min<size_t>((n / 2 + 255) / 256 + 1, 4096);
+    auto g2half = [&](float tf) {      // the reference's fp32 expressions: g = sigma_min (sigma_max / sigma_min)^t sqrt(2 lambda); 0.5 g^2
+      const double lam = std::log((double)oc.sigma_max / (double)oc.sigma_min);
+      const float g = (float)((double)oc.sigma_min * std::pow((double)oc.sigma_max / (double)oc.sigma_min, (double)tf) * std::sqrt(2.0 * lam));
+      return (double)(g * g * 0.5f);
+    };
+    auto base_args = [&]() {
+      OdeArgs a{};
+      a.x = (const float*)xcur; a.y = (const float*)sy_; a.score = (const float*)sscore_;
+      for (int j = 0; j < 7; ++j) a.k[j] = (const float*)K[j];
+      a.table = ode_table_; a.step_ptr = step_ctr_; a.row = -1; a.theta = oc.theta; a.nfl = (long long)(2 * n);
+      a.atol = oc.atol; a.rtol = oc.rtol; a.partial = ode_partial_; a.result = ode_result_;
+      return a;
+    };
+    // stage times + scalar table (+ score-wrapper rows) of one attempt -> device through the pinned staging buffer; time embedding
+    // rows 0..nt-1; step counter to row 0
+    auto upload = [&](const double* times, int nt, double* table) {
+      float tf[ODE_ROWS] = {0}, cf[ODE_ROWS * 4] = {0};
+      for (int e = 0; e < nt; ++e) { tf[e] = (float)times[e]; table[e * ODE_STRIDE] = g2half(tf[e]); }
+      if (oc.coef_fn) {
+        float ga[ODE_ROWS], al[ODE_ROWS], be[ODE_ROWS];
+        oc.coef_fn(oc.coef_user, nt, tf, ga, al, be);
+        for (int e = 0; e < nt; ++e) {
+          SG_REQUIRE(std::isfinite(ga[e]) && std::isfinite(al[e]) && std::isfinite(be[e]), "ode_sample: the score-wrapper callback returned a non-finite coefficient");
+          cf[4 * e] = ga[e]; cf[4 * e + 1] = al[e]; cf[4 * e + 2] = be[e];
+        }
+      }
+      if (hstage_pending_) { SG_CHECK(drt::event_sync(&hstage_ev_)); hstage_pending_ = false; }
+      const size_t nb_t = sizeof tf, nb_c = sizeof cf, nb_tab = sizeof(double) * ODE_ROWS * ODE_STRIDE;
+      SG_REQUIRE(hstage_ && hstage_cap_ >= nb_t + nb_c + nb_tab, "ode_sample: staging buffer missing");
+      memcpy(hstage_, table, nb_tab); memcpy(hstage_ + nb_tab, tf, nb_t); memcpy(hstage_ + nb_tab + nb_t, cf, nb_c);
+      SG_CHECK(drt::memcpy_h2d(ode_table_, hstage_, nb_tab, stream_));
+      SG_CHECK(drt::memcpy_h2d(tsteps_, hstage_ + nb_tab, nb_t, stream_));
+      if (oc.coef_fn) SG_CHECK(drt::memcpy_h2d(coef_table_, hstage_ + nb_tab + nb_t, nb_c, stream_));
+      SG_CHECK(drt::event_record(&hstage_ev_, stream_));
+      hstage_pending_ = true;
+      compute_temb(tsteps_, nt);
+      DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_, 0);
+    };
+    auto evaluate = [&](const float2* at) {      // one network evaluation at the step counter's time row
+      arena_.reset();
+      run_forward(at, FT, sy_, FT, sscore_, B, F, T, ctl);
+    };
+    auto read_sums = [&](double* s) {            // second stage of a reduction + the one scalar transfer of an attempt
+      DRT_LAUNCH(ode_reduce_final_kernel, dim3(1), dim3(64), stream_, (const double*)ode_partial_, ode_result_);
+      SG_CHECK(drt::memcpy_d2h(ode_host_, ode_result_, sizeof(double) * ODE_NSUM, stream_));
+      SG_CHECK(drt::stream_sync(stream_));
+      check_launch();
+      s[0] = ode_host_[0]; s[1] = ode_host_[1];
+    };
+    auto count = [&](int k) {
+      SG_REQUIRE(nfe_ + k <= oc.max_nfe, "ode_sample: the solver needs more than max_nfe = " + std::to_string(oc.max_nfe) + " evaluations (t = " +
+                 std::to_string(ode_t_acc_.empty() ? oc.t_end : ode_t_acc_.back()) + ")");
+      nfe_ += k;
+    };
+
+    double t = oc.t_end;
+    double table[ODE_ROWS * ODE_STRIDE];
+    // f0 = f(t0, y0)
+    count(1);
+    memset(table, 0, sizeof table);
+    upload(&t, 1, table);
+    evaluate(xcur);
+    { OdeArgs a = base_args(); a.xs = a.x; a.kout = (float*)K[0]; a.self = 0; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
+
+    const double max_step = oc.max_step > 0 ? oc.max_step : INFINITY;
+    double h_abs;
+    if (oc.first_step > 0) {
+      h_abs = oc.first_step;
+    } else {      // select_initial_step (Hairer, Norsett, Wanner I, II.4), error estimator order 4
+      count(1);
+      double s[2];
+      { OdeArgs a = base_args(); a.k[1] = nullptr; DRT_LAUNCH(ode_init_norms_kernel, dim3(ODE_NBLK), dim3(256), stream_, a); }
+      read_sums(s);
+      const double d0 = std::sqrt(s[0] / (double)n), d1 = std::sqrt(s[1] / (double)n);
+      double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
+      h0 = std::min(h0, interval);
+      memset(table, 0, sizeof table);
+      table[6 * ODE_STRIDE + 1] = h0 * dir;
+      const double t1 = t + h0 * dir;
+      upload(&t1, 1, table);
+      { OdeArgs a = base_args(); a.row = 6; a.nterms = 1; a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
+      evaluate(ode_xs_);
+      { OdeArgs a = base_args(); a.xs = (const float*)ode_xs_; a.kout = (float*)K[6]; a.self = 6; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
+      { OdeArgs a = base_args(); a.k[0] = (const float*)K[6]; a.k[1] = (const float*)K[0]; DRT_LAUNCH(ode_init_norms_kernel, dim3(ODE_NBLK), dim3(256), stream_, a); }
+      read_sums(s);
+      const double d2 = std::sqrt(s[1] / (double)n) / h0;
+      const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3) : std::pow(0.01 / std::max(d1, d2), 1.0 / 5.0);
+      h_abs = std::min(std::min(100.0 * h0, h1), std::min(interval, max_step));
+    }
+
+    // Dormand-Prince 5(4) tableau (rk.py RK45)
+    static const double Cc[6] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0};
+    static const double Aa[6][5] = {{0, 0, 0, 0, 0},
+                                    {1.0 / 5, 0, 0, 0, 0},
+                                    {3.0 / 40, 9.0 / 40, 0, 0, 0},
+                                    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0},
+                                    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0},
+                                    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656}};
+    static const double Bb[6] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
+    static const double Ee[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
+
+    while (dir * (t - oc.eps) < 0) {
+      const double min_step = 10.0 * std::fabs(std::nextafter(t, dir * INFINITY) - t);
+      if (h_abs > max_step) h_abs = max_step;
+      else if (h_abs < min_step) h_abs = min_step;
+      bool rejected = false;
+      for (;;) {
+        SG_REQUIRE(!(h_abs < min_step), "ode_sample: required step size is less than spacing between numbers (t = " + std::to_string(t) + ")");
+        double h = h_abs * dir, t_new = t + h;
+        if (dir * (t_new - oc.eps) > 0) t_new = oc.eps;
+        h = t_new - t;
+        h_abs = std::fabs(h);
+        count(6);
+        // ---- one attempted step: six evaluations, one scalar back
+        double times[6];
+        for (int e = 0; e < 5; ++e) times[e] = t + Cc[e + 1] * h;
+        times[5] = t + h;
+        memset(table, 0, sizeof table);
+        for (int e = 0; e < 4; ++e) for (int j = 0; j <= e + 1; ++j) table[e * ODE_STRIDE + 1 + j] = h * Aa[e + 2][j];
+        for (int j = 0; j < 6; ++j) table[4 * ODE_STRIDE + 1 + j] = h * Bb[j];
+        for (int j = 0; j < 7; ++j) table[5 * ODE_STRIDE + 1 + j] = h * Ee[j];
+        table[6 * ODE_STRIDE + 1] = h * Aa[1][0];
+        upload(times, 6, table);
+        { OdeArgs a = base_args(); a.row = 6; a.nterms = 1; a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
+        for (int e = 0; e < 5; ++e) {
+          evaluate(ode_xs_);
+          OdeArgs a = base_args();
+          a.xs = (const float*)ode_xs_; a.kout = (float*)K[e + 1]; a.self = e + 1; a.nterms = e + 2;
+          a.xnext = e < 4 ? (float*)ode_xs_ : (float*)xnew;
+          DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a);
+          DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
+        }
+        evaluate(xnew);
+        { OdeArgs a = base_args(); a.xnew = (const float*)xnew; a.kout = (float*)K[6]; DRT_LAUNCH(ode_error_kernel, dim3(ODE_NBLK), dim3(256), stream_, a); }
+        double s[2];
+        read_sums(s);
+        const double norm = std::sqrt(s[0] / (double)n);
+        if (norm < 1.0) {
+          double factor = norm == 0.0 ? 10.0 : std::min(10.0, 0.9 * std::pow(norm, -0.2));
+          if (rejected) factor = std::min(1.0, factor);
+          h_abs *= factor;
+          t = t_new;
+          std::swap(xcur, xnew);
+          std::swap(K[0], K[6]);       // first same as last
+          ++ode_accepted_;
+          ode_t_acc_.push_back(t);
+          break;
+        }
+        const double shrink = 0.9 * std::pow(norm, -0.2);
+        h_abs *= shrink > 0.2 ? shrink : 0.2;      // (a non-finite norm is a rejection with the smallest factor, as max(MIN_FACTOR, nan) is in scipy)
+        rejected = true;
+        ++ode_rejected_;
+      }
+    }
+    SG_CHECK(drt::memcpy_d2d(out, xcur, n * 8, stream_));
+  }
+  void ode_stats(int* accepted, int* rejected, double* t_accepted, int cap) const {
+    if (accepted) *accepted = ode_accepted_;
+    if (rejected) *rejected = ode_rejected_;
+    for (int i = 0; t_accepted && i < cap && i < (int)ode_t_acc_.size(); ++i) t_accepted[i] = ode_t_acc_[i];
   }
   void set_noise_streams(const unsigned long long* ids, int n) { streams_next_.assign(ids, ids + n); }
   void set_ragged_frames(const int* frames, int n) { set_frames(frames, n); }     // sgmse_set_frames
@@ -1941,6 +2170,10 @@ class Engine {
   float *temb_act_ = nullptr, *bias_table_ = nullptr, *step_table_ = nullptr, *tsteps_ = nullptr, *coef_table_ = nullptr; int temb_rows_ = 0;
   drt::graph_t graph_{}; bool graph_valid_ = false; GraphKey graph_key_{};
   int nfe_ = 0;
+  // adaptive ODE sampler (ode_sample): slopes K_0..K_6, stage input, scalar table, reduction buffers, the pinned result, last run's statistics
+  float2* ode_k_[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float2* ode_xs_ = nullptr; size_t ode_n_ = 0;
+  double *ode_table_ = nullptr, *ode_partial_ = nullptr, *ode_result_ = nullptr, *ode_host_ = nullptr;
+  int ode_accepted_ = 0, ode_rejected_ = 0; std::vector<double> ode_t_acc_;
   bool prof_ = false; std::vector<ProfRec> prof_recs_; size_t prof_used_ = 0; float prof_ms_[TC_COUNT]; double prof_flops_[TC_COUNT]; int prof_n_[TC_COUNT];
 };
 
