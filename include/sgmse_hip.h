@@ -137,6 +137,29 @@ int sgmse_ode_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int
 /* the last sgmse_ode_sample run of this context: accepted and rejected step counts and the first min(cap, accepted) accepted time
  * points (the last one is eps exactly after a completed run).  Any of the pointers may be NULL. */
 int sgmse_ode_stats(sgmse_ctx* ctx, int* accepted, int* rejected, double* t_accepted, int cap);
+/* -- the same solver with PER-UTTERANCE step control: every utterance of the batch is integrated as if it were alone -- its own
+ *    initial step, stage times, error norm (over its own F*T_b elements), accept / reject decisions, step count and end of
+ *    integration -- while every network evaluation is still one launch sequence over the whole batch.  Utterance b's result is
+ *    bit-identical to what sgmse_ode_sample gives for that utterance alone (B = 1, same prior: x0 / noise / seed and noise-stream id,
+ *    same cfg), in any batch and any slot, and so are its evaluation count, step counts and accepted times: what the reference's
+ *    one-file-at-a-time enhancement.py loop computes, batched.
+ *    Honours sgmse_set_frames: a ragged context takes T = max_b T_b and PACKED Y / out / x0 / noise (utterance after utterance, [F][T_b]
+ *    each), as sgmse_pc_sample does; otherwise complex64 [B][1][F][T].
+ *    A "round" is one attempted step of every unfinished utterance: six batch evaluations, one table up, B error sums back.  A finished
+ *    utterance is frozen (its slot is still evaluated by the network; nothing of it is written) until the last one has finished.
+ *    cfg: as for sgmse_ode_sample; max_nfe caps EVERY utterance's own count; coef_fn is called once per round (and once per the one
+ *    or two evaluations of the start) with n = stages * B times in STAGE-MAJOR order, t[stage * B + b] (stages = 6 in a round, 1 at the start), and fills its
+ *    three arrays in the same order.
+ *    *nfe_max receives max_b of utterance b's evaluation count (scipy's nfev) = the number of batch evaluations run.
+ *    Errors (SGMSE_ERUNTIME; the message names the utterance and its time; the context stays usable): an utterance needs more than
+ *    max_nfe evaluations, or its step size falls below 10 ulp(t) (a non-finite error norm counts as a rejected step). */
+int sgmse_ode_sample_each(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int T, const sgmse_ode_cfg* cfg, const void* noise,
+                          const void* x0, unsigned long long seed, int* nfe_max);
+/* utterance b of the last sgmse_ode_sample_each run of this context: its evaluation count, accepted and rejected step counts and the
+ * first min(cap, accepted) accepted time points; and of the run as a whole: *rounds, and *wasted = the utterance-evaluations spent on
+ * slots of utterances that had already finished (6 per finished utterance and round; B * *nfe_max is the total).  Any pointer may be NULL. */
+int sgmse_ode_stats_each(sgmse_ctx* ctx, int b, int* nfe, int* accepted, int* rejected, double* t_accepted, int cap, int* rounds,
+                         int* wasted);
 
 /* -- SpecsDataModule.stft / istft / spec_fwd / spec_back (data_module.py:162-188,212-218) ---------------------
  * sig fp32 [B][L] -> spec complex64 [B][n_fft/2+1][L/hop+1] (center=True, reflect pad, window fp32 [n_fft]). */

@@ -68,6 +68,8 @@ _SIGS = {
     "sgmse_sb_sample": (_I, [_P, _P, _P, _I, _I, _I, _I] + [C.POINTER(_F)] * 8 + [_I, _P, C.c_ulonglong, _I, C.POINTER(_I)]),
     "sgmse_ode_sample": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(OdeCfgC), _P, _P, C.c_ulonglong, C.POINTER(_I)]),
     "sgmse_ode_stats": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_double), _I]),
+    "sgmse_ode_sample_each": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(OdeCfgC), _P, _P, C.c_ulonglong, C.POINTER(_I)]),
+    "sgmse_ode_stats_each": (_I, [_P, _I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(C.c_double), _I, C.POINTER(_I), C.POINTER(_I)]),
     "sgmse_stft": (_I, [_P, _P, _P, _P, _I, _I, _I, _I]),
     "sgmse_istft": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "sgmse_spec_fwd": (_I, [_P, _P, _P, _LL, _I, _F, _F]),
@@ -403,13 +405,26 @@ class Context:
 
     def ode_sample(self, Y: torch.Tensor, *, theta: float, sigma_min: float, sigma_max: float, std1: float, t_end: float, eps: float,
                    rtol: float, atol: float, first_step: float = 0.0, max_step: float = 0.0, noise: Optional[torch.Tensor] = None,
-                   x0: Optional[torch.Tensor] = None, seed: int = 0, streams=None, affine_fn=None, max_nfe: int = 100000):
+                   x0: Optional[torch.Tensor] = None, seed: int = 0, streams=None, affine_fn=None, max_nfe: int = 100000,
+                   step_control: str = "batch"):
         """Adaptive probability-flow sampler inside the library (sgmse_ode_sample): Dormand-Prince 5(4) with scipy's RK45 step
         control, state and stage slopes on the device.  ``x0``: the start state itself; else the prior y + std1 z with ``noise``
         ([B,1,F,T], or the samplers' [ndraws,B,1,F,T] layout whose first entry is the prior draw) or the Philox stream of
         (``seed``, ``streams``).  ``affine_fn``: ``ScoreModel.score_affine`` of an ncsnpp_v2 model (None: old-code wrapper), called
         with each attempted step's stage times.  Returns (sample, nfe); ``ode_stats`` describes the run.  Raises RuntimeError when
-        the solver needs more than ``max_nfe`` evaluations or its step size underflows."""
+        the solver needs more than ``max_nfe`` evaluations or its step size underflows.
+
+        ``step_control="utterance"`` (sgmse_ode_sample_each): every utterance is integrated as if it were alone -- its result, bit for
+        bit, and its counts are those of its own single-utterance call -- while each network evaluation still covers the whole batch.
+        ``Y`` (and ``x0``) may then be a ragged list of [F,T_b] / [1,F,T_b] spectrograms (``set_frames``; the samples come back as a
+        list of [1,F,T_b]); ``max_nfe`` caps every utterance's own count, ``affine_fn`` sees a round's 6 B stage times stage-major,
+        the returned nfe is the largest utterance's, and ``ode_stats_each`` describes the run."""
+        if step_control not in ("batch", "utterance"):
+            raise ValueError(f"step_control must be 'batch' or 'utterance', got {step_control!r}")
+        if step_control == "utterance":
+            return self._ode_sample_each(Y, dict(theta=theta, sigma_min=sigma_min, sigma_max=sigma_max, std1=std1, t_end=t_end, eps=eps,
+                                                 rtol=rtol, atol=atol, first_step=first_step, max_step=max_step, max_nfe=max_nfe),
+                                         noise, x0, seed, streams, affine_fn)
         if isinstance(Y, (list, tuple)):
             raise TypeError("the adaptive ODE sampler integrates one rectangular batch (its error norm couples the utterances): "
                             "pass a tensor, not a ragged list")
@@ -429,25 +444,8 @@ class Context:
             x0 = check_tensor(x0, "z", torch.complex64, self.device)
             if tuple(x0.shape) != tuple(Y.shape):
                 raise ValueError(f"the start state must have y's shape {tuple(Y.shape)}, got {tuple(x0.shape)}")
-        cfg = OdeCfgC()
-        cfg.theta, cfg.sigma_min, cfg.sigma_max, cfg.std1 = float(theta), float(sigma_min), float(sigma_max), float(std1)
-        cfg.t_end, cfg.eps, cfg.rtol, cfg.atol = float(t_end), float(eps), float(rtol), float(atol)
-        cfg.first_step, cfg.max_step, cfg.max_nfe = float(first_step), float(max_step), int(max_nfe)
-        failure = []
-        if affine_fn is not None:
-            def _coef(user, n, t, gamma, alpha, beta):      # host callback: exceptions must not cross the C frames
-                try:
-                    rows = affine_fn(torch.tensor([t[i] for i in range(n)], dtype=torch.float32))
-                    for dst, v in zip((gamma, alpha, beta), rows):
-                        v = torch.as_tensor(v, dtype=torch.float32).reshape(-1).expand(n)
-                        for i in range(n):
-                            dst[i] = float(v[i])
-                except Exception as e:      # noqa: BLE001
-                    failure.append(e)
-                    for i in range(n):
-                        gamma[i] = alpha[i] = beta[i] = float("nan")
-            cb = ODE_COEF_FN(_coef)
-            cfg.coef_fn = cb
+        cfg, failure, cb = self._ode_cfg(dict(theta=theta, sigma_min=sigma_min, sigma_max=sigma_max, std1=std1, t_end=t_end, eps=eps, rtol=rtol,
+                                              atol=atol, first_step=first_step, max_step=max_step, max_nfe=max_nfe), affine_fn)
         if streams is not None:
             if len(streams) != B:
                 raise ValueError(f"streams must name the {B} utterances of the batch, got {len(streams)}")
@@ -464,6 +462,96 @@ class Context:
             raise failure[0]
         self.check(rc)
         return out, nfe.value
+
+    @staticmethod
+    def _ode_cfg(v, affine_fn):
+        """sgmse_ode_cfg of one call: (cfg, failure list of the host callback, the callback object to keep alive)."""
+        cfg = OdeCfgC()
+        cfg.theta, cfg.sigma_min, cfg.sigma_max, cfg.std1 = float(v["theta"]), float(v["sigma_min"]), float(v["sigma_max"]), float(v["std1"])
+        cfg.t_end, cfg.eps, cfg.rtol, cfg.atol = float(v["t_end"]), float(v["eps"]), float(v["rtol"]), float(v["atol"])
+        cfg.first_step, cfg.max_step, cfg.max_nfe = float(v["first_step"]), float(v["max_step"]), int(v["max_nfe"])
+        failure, cb = [], None
+        if affine_fn is not None:
+            def _coef(user, n, t, gamma, alpha, beta):      # host callback: exceptions must not cross the C frames
+                try:
+                    rows = affine_fn(torch.tensor([t[i] for i in range(n)], dtype=torch.float32))
+                    for dst, v in zip((gamma, alpha, beta), rows):
+                        v = torch.as_tensor(v, dtype=torch.float32).reshape(-1).expand(n)
+                        for i in range(n):
+                            dst[i] = float(v[i])
+                except Exception as e:      # noqa: BLE001
+                    failure.append(e)
+                    for i in range(n):
+                        gamma[i] = alpha[i] = beta[i] = float("nan")
+            cb = ODE_COEF_FN(_coef)
+            cfg.coef_fn = cb
+        return cfg, failure, cb
+
+    def _ode_sample_each(self, Y, values, noise, x0, seed, streams, affine_fn):
+        """``ode_sample(step_control="utterance")``: sgmse_ode_sample_each over a tensor [B,1,F,T] or a ragged list."""
+        frames = None
+        if isinstance(Y, (list, tuple)):
+            if noise is not None:
+                raise ValueError("ragged batches take the prior from seed / streams or a start state z, not from replayed noise")
+            frames, F_ = _ragged_geometry(Y, 1, "y")
+            B, T = len(Y), max(frames)
+            Y = torch.cat([check_tensor(y, "y", torch.complex64, self.device).reshape(-1) for y in Y])
+            if x0 is not None:
+                if not isinstance(x0, (list, tuple)) or len(x0) != B or _ragged_geometry(x0, 1, "z") != (frames, F_):
+                    raise ValueError("the start state of a ragged batch is a list with the shapes of y's utterances")
+                x0 = torch.cat([check_tensor(x, "z", torch.complex64, self.device).reshape(-1) for x in x0])
+        else:
+            Y = check_tensor(Y, "y", torch.complex64, self.device)
+            if Y.dim() != 4 or Y.shape[1] != 1:
+                raise ValueError(f"expected y of shape [B,1,F,T], got {tuple(Y.shape)}")
+            B, _, F_, T = Y.shape
+            if noise is not None and x0 is not None:
+                raise ValueError("give replayed noise or a start state, not both")
+            if noise is not None:
+                noise = check_tensor(noise, "noise", torch.complex64, self.device)
+                if noise.dim() == Y.dim() + 1:
+                    noise = noise[0].contiguous()
+                if tuple(noise.shape) != tuple(Y.shape):
+                    raise ValueError(f"noise must be [{B},1,{F_},{T}] complex64 (or [ndraws,{B},1,{F_},{T}]), got {tuple(noise.shape)}")
+            if x0 is not None:
+                x0 = check_tensor(x0, "z", torch.complex64, self.device)
+                if tuple(x0.shape) != tuple(Y.shape):
+                    raise ValueError(f"the start state must have y's shape {tuple(Y.shape)}, got {tuple(x0.shape)}")
+        cfg, failure, cb = self._ode_cfg(values, affine_fn)
+        if streams is not None:
+            if len(streams) != B:
+                raise ValueError(f"streams must name the {B} utterances of the batch, got {len(streams)}")
+            self.set_noise_streams(streams)
+        out = torch.empty_like(Y)
+        nfe = _I(0)
+        self.use_current_stream()
+        self.set_frames(frames if frames is not None else [])
+        rc = self.lib.sgmse_ode_sample_each(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, C.byref(cfg), ptr(noise), ptr(x0),
+                                            C.c_ulonglong(seed & (2 ** 64 - 1)), C.byref(nfe))
+        if failure:
+            raise failure[0]
+        self.check(rc)
+        self._ode_each_B = B
+        if frames is not None:                  # unpack: one [1,F,T_b] tensor per utterance
+            outs, o = [], 0
+            for T_b in frames:
+                outs.append(out[o:o + F_ * T_b].reshape(1, F_, T_b))
+                o += F_ * T_b
+            return outs, nfe.value
+        return out, nfe.value
+
+    def ode_stats_each(self):
+        """The last ``ode_sample(step_control="utterance")`` run: dict(utterances=[dict(nfe=..., accepted=..., rejected=...,
+        t=[accepted time points]) per utterance], rounds=attempted-step rounds, wasted=utterance-evaluations spent on slots of
+        utterances that had already finished)."""
+        utts, rounds, wasted = [], _I(0), _I(0)
+        for b in range(getattr(self, "_ode_each_B", 0)):
+            nfe, acc, rej = _I(0), _I(0), _I(0)
+            self.check(self.lib.sgmse_ode_stats_each(self.h, b, C.byref(nfe), C.byref(acc), C.byref(rej), None, 0, None, None))
+            ts = (C.c_double * max(acc.value, 1))()
+            self.check(self.lib.sgmse_ode_stats_each(self.h, b, None, None, None, ts, acc.value, C.byref(rounds), C.byref(wasted)))
+            utts.append(dict(nfe=nfe.value, accepted=acc.value, rejected=rej.value, t=[ts[i] for i in range(acc.value)]))
+        return dict(utterances=utts, rounds=rounds.value, wasted=wasted.value)
 
     def ode_stats(self):
         """The last ``ode_sample`` run: dict(accepted=..., rejected=..., t=[accepted time points])."""

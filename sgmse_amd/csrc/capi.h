@@ -146,6 +146,30 @@ int sgmse_ode_stats(sgmse_ctx* ctx, int* accepted, int* rejected, double* t_acce
   return sg_guard(ctx, [&](sgmse::Engine& e) { e.ode_stats(accepted, rejected, t_accepted, cap); });
 }
 
+int sgmse_ode_sample_each(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int T, const sgmse_ode_cfg* cfg, const void* noise,
+                          const void* x0, unsigned long long seed, int* nfe_max) {
+  SG_ARG(ctx, Y && out && cfg && B > 0 && F > 0 && T > 0, "null pointer or non-positive shape");
+  SG_ARG(ctx, cfg->rtol > 0 && cfg->atol >= 0, "rtol must be positive and atol non-negative");
+  SG_ARG(ctx, cfg->first_step >= 0 && cfg->max_step >= 0, "first_step and max_step must not be negative (0: automatic / no limit)");
+  SG_ARG(ctx, cfg->max_nfe >= 1, "max_nfe must be >= 1");
+  SG_ARG(ctx, !(noise && x0), "give replayed noise or a start state, not both");
+  return sg_guard(ctx, [&](sgmse::Engine& e) {
+    sgmse::OdeCfg o;
+    o.theta = cfg->theta; o.sigma_min = cfg->sigma_min; o.sigma_max = cfg->sigma_max; o.std1 = cfg->std1;
+    o.t_end = cfg->t_end; o.eps = cfg->eps; o.rtol = cfg->rtol; o.atol = cfg->atol; o.first_step = cfg->first_step;
+    o.max_step = cfg->max_step; o.max_nfe = cfg->max_nfe; o.coef_fn = cfg->coef_fn; o.coef_user = cfg->coef_user;
+    try { e.ode_sample_each((const float2*)Y, (float2*)out, B, F, T, o, (const float2*)noise, (const float2*)x0, seed); }
+    catch (...) { if (nfe_max) *nfe_max = e.last_nfe(); throw; }
+    if (nfe_max) *nfe_max = e.last_nfe();
+  });
+}
+
+int sgmse_ode_stats_each(sgmse_ctx* ctx, int b, int* nfe, int* accepted, int* rejected, double* t_accepted, int cap, int* rounds,
+                         int* wasted) {
+  SG_ARG(ctx, cap >= 0 && (t_accepted != nullptr || cap == 0), "bad time buffer");
+  return sg_guard(ctx, [&](sgmse::Engine& e) { e.ode_stats_each(b, nfe, accepted, rejected, t_accepted, cap, rounds, wasted); });
+}
+
 int sgmse_stft(sgmse_ctx* ctx, const float* sig, const float* window, void* spec, int B, int L, int n_fft, int hop) {
   SG_ARG(ctx, sig && window && spec && B > 0 && L > 0, "null pointer or non-positive shape");
   return sg_guard(ctx, [&](sgmse::Engine& e) { e.op_stft(sig, window, (float2*)spec, B, L, n_fft, hop); });

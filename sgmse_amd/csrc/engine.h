@@ -20,6 +20,8 @@
 #include "kernels_norm_fir.h"
 #include "kernels_attn_misc.h"
 #include "kernels_ode.h"
+#include "kernels_ode_each.h"
+#include "ode_control.h"
 #include "kernels_stft.h"
 
 namespace sgmse {
@@ -345,6 +347,7 @@ class Engine {
     if (graph_valid_ || graph_stale_) drt::graph_destroy(&graph_);
     if (hstage_) drt::free_host(hstage_);
     if (ode_host_) drt::free_host(ode_host_);
+    if (ode_ehost_) drt::free_host(ode_ehost_);
     if (hstage_ev_init_) drt::event_destroy(&hstage_ev_);
     for (drt::event_t& e : side_ev_) drt::event_destroy(&e);
     if (side_stream_ready_) drt::stream_destroy(side_stream_);
@@ -564,6 +567,12 @@ class Engine {
     SG_CHECK(drt::memcpy_d2d(out, sx_, n * 8, stream_));
     nfe_ = N;
   }
+  // the reference's fp32 expressions: g = sigma_min (sigma_max / sigma_min)^t sqrt(2 lambda); 0.5 g^2
+  static double ode_g2half(const OdeCfg& oc, float tf) {
+    const double lam = std::log((double)oc.sigma_max / (double)oc.sigma_min);
+    const float g = (float)((double)oc.sigma_min * std::pow((double)oc.sigma_max / (double)oc.sigma_min, (double)tf) * std::sqrt(2.0 * lam));
+    return (double)(g * g * 0.5f);
+  }
   // get_ode_sampler(..., denoise=False)() (sampling/__init__.py:96-143) with the solver inside the library: scipy's RK45
   // (Dormand-Prince 5(4), scipy/integrate/_ivp/rk.py) and its step control (common.py select_initial_step, RungeKutta._step_impl)
   // over the flattened batch -- ONE error norm for all B*F*T complex elements, as scipy sees the state, so the utterances of a batch
@@ -616,11 +625,6 @@ class Engine {
     if (oc.coef_fn) { ctl.coef = coef_table_; ctl.coef_bstride = 0; ctl.coef_sstride = 1; }
     const long long FT = (long long)F * T;
     const unsigned egrid = (unsigned)std::min<size_t>((n / 2 + 255) / 256 + 1, 4096);
-    auto g2half = [&](float tf) {      // the reference's fp32 expressions: g = sigma_min (sigma_max / sigma_min)^t sqrt(2 lambda); 0.5 g^2
-      const double lam = std::log((double)oc.sigma_max / (double)oc.sigma_min);
-      const float g = (float)((double)oc.sigma_min * std::pow((double)oc.sigma_max / (double)oc.sigma_min, (double)tf) * std::sqrt(2.0 * lam));
-      return (double)(g * g * 0.5f);
-    };
     auto base_args = [&]() {
       OdeArgs a{};
       a.x = (const float*)xcur; a.y = (const float*)sy_; a.score = (const float*)sscore_;
@@ -633,7 +637,7 @@ class Engine {
     // rows 0..nt-1; step counter to row 0
     auto upload = [&](const double* times, int nt, double* table) {
       float tf[ODE_ROWS] = {0}, cf[ODE_ROWS * 4] = {0};
-      for (int e = 0; e < nt; ++e) { tf[e] = (float)times[e]; table[e * ODE_STRIDE] = g2half(tf[e]); }
+      for (int e = 0; e < nt; ++e) { tf[e] = (float)times[e]; table[e * ODE_STRIDE] = ode_g2half(oc, tf[e]); }
       if (oc.coef_fn) {
         float ga[ODE_ROWS], al[ODE_ROWS], be[ODE_ROWS];
         oc.coef_fn(oc.coef_user, nt, tf, ga, al, be);
@@ -671,107 +675,276 @@ class Engine {
       nfe_ += k;
     };
 
-    double t = oc.t_end;
+    OdeControl c;                  // the step control (ode_control.h): one controller for the whole flattened batch
+    c.start(oc.t_end, oc.eps, oc.max_step, (double)n);
     double table[ODE_ROWS * ODE_STRIDE];
     // f0 = f(t0, y0)
     count(1);
     memset(table, 0, sizeof table);
-    upload(&t, 1, table);
+    upload(&c.t, 1, table);
     evaluate(xcur);
     { OdeArgs a = base_args(); a.xs = a.x; a.kout = (float*)K[0]; a.self = 0; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
 
-    const double max_step = oc.max_step > 0 ? oc.max_step : INFINITY;
-    double h_abs;
     if (oc.first_step > 0) {
-      h_abs = oc.first_step;
-    } else {      // select_initial_step (Hairer, Norsett, Wanner I, II.4), error estimator order 4
+      c.h_abs = oc.first_step;
+    } else {      // select_initial_step
       count(1);
       double s[2];
       { OdeArgs a = base_args(); a.k[1] = nullptr; DRT_LAUNCH(ode_init_norms_kernel, dim3(ODE_NBLK), dim3(256), stream_, a); }
       read_sums(s);
-      const double d0 = std::sqrt(s[0] / (double)n), d1 = std::sqrt(s[1] / (double)n);
-      double h0 = (d0 < 1e-5 || d1 < 1e-5) ? 1e-6 : 0.01 * d0 / d1;
-      h0 = std::min(h0, interval);
+      const double h0 = c.probe_step(s[0], s[1]);
       memset(table, 0, sizeof table);
-      table[6 * ODE_STRIDE + 1] = h0 * dir;
-      const double t1 = t + h0 * dir;
+      table[6 * ODE_STRIDE + 1] = h0 * c.dir;
+      const double t1 = c.t + h0 * c.dir;
       upload(&t1, 1, table);
       { OdeArgs a = base_args(); a.row = 6; a.nterms = 1; a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
       evaluate(ode_xs_);
       { OdeArgs a = base_args(); a.xs = (const float*)ode_xs_; a.kout = (float*)K[6]; a.self = 6; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
       { OdeArgs a = base_args(); a.k[0] = (const float*)K[6]; a.k[1] = (const float*)K[0]; DRT_LAUNCH(ode_init_norms_kernel, dim3(ODE_NBLK), dim3(256), stream_, a); }
       read_sums(s);
-      const double d2 = std::sqrt(s[1] / (double)n) / h0;
-      const double h1 = (d1 <= 1e-15 && d2 <= 1e-15) ? std::max(1e-6, h0 * 1e-3) : std::pow(0.01 / std::max(d1, d2), 1.0 / 5.0);
-      h_abs = std::min(std::min(100.0 * h0, h1), std::min(interval, max_step));
+      c.first_step_from_probe(s[1]);
     }
 
-    // Dormand-Prince 5(4) tableau (rk.py RK45)
-    static const double Cc[6] = {0.0, 1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0};
-    static const double Aa[6][5] = {{0, 0, 0, 0, 0},
-                                    {1.0 / 5, 0, 0, 0, 0},
-                                    {3.0 / 40, 9.0 / 40, 0, 0, 0},
-                                    {44.0 / 45, -56.0 / 15, 32.0 / 9, 0, 0},
-                                    {19372.0 / 6561, -25360.0 / 2187, 64448.0 / 6561, -212.0 / 729, 0},
-                                    {9017.0 / 3168, -355.0 / 33, 46732.0 / 5247, 49.0 / 176, -5103.0 / 18656}};
-    static const double Bb[6] = {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84};
-    static const double Ee[7] = {-71.0 / 57600, 0, 71.0 / 16695, -71.0 / 1920, 17253.0 / 339200, -22.0 / 525, 1.0 / 40};
-
-    while (dir * (t - oc.eps) < 0) {
-      const double min_step = 10.0 * std::fabs(std::nextafter(t, dir * INFINITY) - t);
-      if (h_abs > max_step) h_abs = max_step;
-      else if (h_abs < min_step) h_abs = min_step;
-      bool rejected = false;
-      for (;;) {
-        SG_REQUIRE(!(h_abs < min_step), "ode_sample: required step size is less than spacing between numbers (t = " + std::to_string(t) + ")");
-        double h = h_abs * dir, t_new = t + h;
-        if (dir * (t_new - oc.eps) > 0) t_new = oc.eps;
-        h = t_new - t;
-        h_abs = std::fabs(h);
-        count(6);
-        // ---- one attempted step: six evaluations, one scalar back
-        double times[6];
-        for (int e = 0; e < 5; ++e) times[e] = t + Cc[e + 1] * h;
-        times[5] = t + h;
-        memset(table, 0, sizeof table);
-        for (int e = 0; e < 4; ++e) for (int j = 0; j <= e + 1; ++j) table[e * ODE_STRIDE + 1 + j] = h * Aa[e + 2][j];
-        for (int j = 0; j < 6; ++j) table[4 * ODE_STRIDE + 1 + j] = h * Bb[j];
-        for (int j = 0; j < 7; ++j) table[5 * ODE_STRIDE + 1 + j] = h * Ee[j];
-        table[6 * ODE_STRIDE + 1] = h * Aa[1][0];
-        upload(times, 6, table);
-        { OdeArgs a = base_args(); a.row = 6; a.nterms = 1; a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
-        for (int e = 0; e < 5; ++e) {
-          evaluate(ode_xs_);
-          OdeArgs a = base_args();
-          a.xs = (const float*)ode_xs_; a.kout = (float*)K[e + 1]; a.self = e + 1; a.nterms = e + 2;
-          a.xnext = e < 4 ? (float*)ode_xs_ : (float*)xnew;
-          DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a);
-          DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
-        }
-        evaluate(xnew);
-        { OdeArgs a = base_args(); a.xnew = (const float*)xnew; a.kout = (float*)K[6]; DRT_LAUNCH(ode_error_kernel, dim3(ODE_NBLK), dim3(256), stream_, a); }
-        double s[2];
-        read_sums(s);
-        const double norm = std::sqrt(s[0] / (double)n);
-        if (norm < 1.0) {
-          double factor = norm == 0.0 ? 10.0 : std::min(10.0, 0.9 * std::pow(norm, -0.2));
-          if (rejected) factor = std::min(1.0, factor);
-          h_abs *= factor;
-          t = t_new;
-          std::swap(xcur, xnew);
-          std::swap(K[0], K[6]);       // first same as last
-          ++ode_accepted_;
-          ode_t_acc_.push_back(t);
-          break;
-        }
-        const double shrink = 0.9 * std::pow(norm, -0.2);
-        h_abs *= shrink > 0.2 ? shrink : 0.2;      // (a non-finite norm is a rejection with the smallest factor, as max(MIN_FACTOR, nan) is in scipy)
-        rejected = true;
+    while (!c.done()) {
+      SG_REQUIRE(c.begin_attempt(), "ode_sample: required step size is less than spacing between numbers (t = " + std::to_string(c.t) + ")");
+      count(6);
+      // ---- one attempted step: six evaluations, one scalar back
+      double times[6];
+      memset(table, 0, sizeof table);
+      c.fill_attempt(times, table, ODE_STRIDE);
+      upload(times, 6, table);
+      { OdeArgs a = base_args(); a.row = 6; a.nterms = 1; a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
+      for (int e = 0; e < 5; ++e) {
+        evaluate(ode_xs_);
+        OdeArgs a = base_args();
+        a.xs = (const float*)ode_xs_; a.kout = (float*)K[e + 1]; a.self = e + 1; a.nterms = e + 2;
+        a.xnext = e < 4 ? (float*)ode_xs_ : (float*)xnew;
+        DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a);
+        DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
+      }
+      evaluate(xnew);
+      { OdeArgs a = base_args(); a.xnew = (const float*)xnew; a.kout = (float*)K[6]; DRT_LAUNCH(ode_error_kernel, dim3(ODE_NBLK), dim3(256), stream_, a); }
+      double s[2];
+      read_sums(s);
+      if (c.finish_attempt(s[0])) {
+        std::swap(xcur, xnew);
+        std::swap(K[0], K[6]);       // first same as last
+        ++ode_accepted_;
+        ode_t_acc_.push_back(c.t);
+      } else {
         ++ode_rejected_;
       }
     }
     SG_CHECK(drt::memcpy_d2d(out, xcur, n * 8, stream_));
   }
+  // The same solver with PER-UTTERANCE step control (kernels_ode_each.h): B controllers, one per utterance of a uniform or ragged
+  // (sgmse_set_frames: packed tensors, as pc_sample takes them) batch, each with its own initial step, stage times, error norm,
+  // accept / reject decisions and end of integration, all fed by ONE batch evaluation per stage.  A "round" is one attempted step of
+  // every unfinished utterance: six batch evaluations at 6 B time-embedding rows (row = stage * B + utterance), one table of
+  // [B][ODE_ROWS][ODE_STRIDE] doubles up, B error sums back.  Utterance b's result, evaluation count, step counts and accepted times
+  // are those of ode_sample on that utterance alone (B = 1): same controller code, same kernels bodies, same summation order.  A
+  // finished utterance is frozen: the network still evaluates its slot (at its last stage input, at t = eps), nothing of it is written.
+  // coef_fn is called once per round with the 6 B stage times STAGE-MAJOR (t[stage * B + b]); max_nfe caps every utterance's own count.
+  void ode_sample_each(const float2* Y, float2* out, int B, int F, int T, const OdeCfg& oc, const float2* noise, const float2* x0,
+                       unsigned long long seed) {
+    require_ready();
+    SG_REQUIRE(oc.t_end != oc.eps && oc.eps > 0 && oc.t_end > 0, "ode_sample_each: bad time span");
+    SG_REQUIRE(oc.sigma_min > 0 && oc.sigma_max > oc.sigma_min, "ode_sample_each: bad sigma range");
+    const double interval = std::fabs(oc.eps - oc.t_end);
+    SG_REQUIRE(oc.first_step <= interval, "ode_sample_each: `first_step` exceeds bounds");
+    SG_REQUIRE(B <= kOdeEachMaxB, "ode_sample_each: batch too large");
+    ensure_shape(B, F, T, ODE_ROWS * B);
+    const size_t n = ragged() ? rag_pix_[0] : (size_t)B * F * T;     // complex elements, utterance after utterance
+    if (n > ode_n_) {
+      for (float2** q : {&ode_k_[0], &ode_k_[1], &ode_k_[2], &ode_k_[3], &ode_k_[4], &ode_k_[5], &ode_k_[6], &ode_xs_}) {
+        if (*q) dev_free_owned(*q);
+        *q = static_cast<float2*>(dev_alloc(n * 8));
+      }
+      ode_n_ = n;
+    }
+    if (B > ode_each_cap_) {
+      for (double** q : {&ode_etable_, &ode_epartial_, &ode_eresult_}) if (*q) dev_free_owned(*q);
+      if (ode_ehost_) drt::free_host(ode_ehost_);
+      ode_etable_ = static_cast<double*>(dev_alloc(sizeof(double) * B * ODE_ROWS * ODE_STRIDE));
+      ode_epartial_ = static_cast<double*>(dev_alloc(sizeof(double) * B * ODE_NBLK * ODE_NSUM));
+      ode_eresult_ = static_cast<double*>(dev_alloc(sizeof(double) * B * ODE_NSUM));
+      ode_ehost_ = nullptr;
+      SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&ode_ehost_), sizeof(double) * B * ODE_NSUM));
+      ode_each_cap_ = B;
+    }
+    ode_each_.assign(B, OdeControl());
+    ode_rounds_ = ode_wasted_ = 0; nfe_ = 0;
+    std::vector<OdeControl>& cs = ode_each_;
+    std::vector<double> npix(B);
+    for (int b = 0; b < B; ++b) {
+      npix[b] = ragged() ? (double)F * rag_T_[b] : (double)F * T;
+      cs[b].start(oc.t_end, oc.eps, oc.max_step, npix[b]);
+    }
+
+    // prior
+    const std::vector<float> one_row(SC_STRIDE, 0.f), one_t(1, (float)oc.t_end);
+    const unsigned long long* seed_dev = upload_tables(one_row, one_t, std::vector<float>(), seed, B);
+    SG_CHECK(drt::memcpy_d2d(sy_, Y, n * 8, stream_));
+    if (x0) {
+      SG_CHECK(drt::memcpy_d2d(sx_, x0, n * 8, stream_));
+    } else {
+      SamplerArgs sa{};
+      sa.x = sx_; sa.y = sy_; sa.noise = noise; sa.seed = seed_dev; sa.std1 = oc.std1; sa.n = (int)n; sa.B = B; sa.per = F * T;
+      sa.rag_off = ragged() ? rag_off_dev_[0] : nullptr;
+      DRT_LAUNCH(sampler_prior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), stream_, sa);
+    }
+
+    // time-embedding / time / wrapper rows: row = stage * B + utterance
+    FwdCtl ctl{bias_table_, tot_temb_, B * tot_temb_, step_ctr_, tsteps_, 1, B, -1.0f};
+    if (oc.coef_fn) { ctl.coef = coef_table_; ctl.coef_bstride = 1; ctl.coef_sstride = B; }
+    const long long FT = ragged() ? 1 : (long long)F * T;            // batch stride of x / y (ragged: multiplier of the utterance's offset)
+    const unsigned egrid = (unsigned)std::min<size_t>(((size_t)F * T / 2 + 255) / 256 + 1, 4096);      // per utterance
+    std::vector<int> sel(B, 0);                                        // host copy of the selectors (kernels_ode_each.h)
+    auto base_args = [&]() {
+      OdeEachArgs e{};
+      OdeArgs& a = e.a;
+      a.y = (const float*)sy_; a.score = (const float*)sscore_;
+      for (int j = 1; j < 6; ++j) a.k[j] = (const float*)ode_k_[j];
+      a.table = ode_etable_; a.step_ptr = step_ctr_; a.row = -1; a.theta = oc.theta;
+      a.atol = oc.atol; a.rtol = oc.rtol; a.partial = ode_epartial_; a.result = ode_eresult_;
+      e.xbuf[0] = (float*)sx_; e.xbuf[1] = (float*)sxm_; e.kbuf[0] = (float*)ode_k_[0]; e.kbuf[1] = (float*)ode_k_[6];
+      e.rag_off = ragged() ? rag_off_dev_[0] : nullptr; e.per = (long long)F * T; e.kout_sel = -1;
+      return e;
+    };
+    const size_t tab_doubles = (size_t)B * ODE_ROWS * ODE_STRIDE;
+    std::vector<double> table(tab_doubles), times((size_t)ODE_ROWS * B);
+    std::vector<float> tf((size_t)ODE_ROWS * B), cf((size_t)ODE_ROWS * B * 4), ga((size_t)ODE_ROWS * B), al(ga.size()), be(ga.size());
+    // one round's table (rows 0..6 of the active utterances filled by the caller; row 7 = selector, active flag), nt * B stage times
+    // (times[e * B + b]) and wrapper rows -> device through the pinned staging buffer; time embedding rows; step counter to row 0
+    auto upload = [&](int nt, const std::vector<char>& active) {
+      const int rows = nt * B;
+      for (int b = 0; b < B; ++b) {
+        double* tb = &table[(size_t)b * ODE_ROWS * ODE_STRIDE];
+        for (int e = 0; e < nt; ++e) { tf[(size_t)e * B + b] = (float)times[(size_t)e * B + b]; tb[e * ODE_STRIDE] = ode_g2half(oc, tf[(size_t)e * B + b]); }
+        tb[ODE_ROW_STATE * ODE_STRIDE] = (double)sel[b]; tb[ODE_ROW_STATE * ODE_STRIDE + 1] = active[b] ? 1.0 : 0.0;
+      }
+      if (oc.coef_fn) {
+        oc.coef_fn(oc.coef_user, rows, tf.data(), ga.data(), al.data(), be.data());
+        for (int r = 0; r < rows; ++r) {
+          SG_REQUIRE(std::isfinite(ga[r]) && std::isfinite(al[r]) && std::isfinite(be[r]), "ode_sample_each: the score-wrapper callback returned a non-finite coefficient");
+          cf[4 * (size_t)r] = ga[r]; cf[4 * (size_t)r + 1] = al[r]; cf[4 * (size_t)r + 2] = be[r]; cf[4 * (size_t)r + 3] = 0.f;
+        }
+      }
+      if (hstage_pending_) { SG_CHECK(drt::event_sync(&hstage_ev_)); hstage_pending_ = false; }
+      const size_t nb_tab = sizeof(double) * tab_doubles, nb_t = sizeof(float) * rows, nb_c = sizeof(float) * 4 * rows;
+      if (nb_tab + nb_t + nb_c > hstage_cap_) {
+        if (hstage_) drt::free_host(hstage_);
+        hstage_ = nullptr; hstage_cap_ = 0;
+        SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&hstage_), nb_tab + nb_t + nb_c));
+        hstage_cap_ = nb_tab + nb_t + nb_c;
+      }
+      memcpy(hstage_, table.data(), nb_tab); memcpy(hstage_ + nb_tab, tf.data(), nb_t); memcpy(hstage_ + nb_tab + nb_t, cf.data(), nb_c);
+      SG_CHECK(drt::memcpy_h2d(ode_etable_, hstage_, nb_tab, stream_));
+      SG_CHECK(drt::memcpy_h2d(tsteps_, hstage_ + nb_tab, nb_t, stream_));
+      if (oc.coef_fn) SG_CHECK(drt::memcpy_h2d(coef_table_, hstage_ + nb_tab + nb_t, nb_c, stream_));
+      SG_CHECK(drt::event_record(&hstage_ev_, stream_));
+      hstage_pending_ = true;
+      compute_temb(tsteps_, rows);
+      DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_, 0);
+    };
+    auto evaluate = [&](const float2* at) {      // one batch evaluation at the step counter's time rows
+      arena_.reset();
+      run_forward(at, FT, sy_, FT, sscore_, B, F, T, ctl);
+      ++nfe_;
+    };
+    auto read_sums = [&]() {                     // second stage of a reduction + the one transfer of a round: B x ODE_NSUM doubles
+      DRT_LAUNCH(ode_reduce_final_each_kernel, dim3(B), dim3(64), stream_, (const double*)ode_etable_, (const double*)ode_epartial_, ode_eresult_);
+      SG_CHECK(drt::memcpy_d2h(ode_ehost_, ode_eresult_, sizeof(double) * B * ODE_NSUM, stream_));
+      SG_CHECK(drt::stream_sync(stream_));
+      check_launch();
+    };
+    auto count = [&](int b, int k) {
+      SG_REQUIRE(cs[b].nfe + k <= oc.max_nfe, "ode_sample_each: utterance " + std::to_string(b) + " needs more than max_nfe = " + std::to_string(oc.max_nfe) +
+                 " evaluations (t = " + std::to_string(cs[b].last_time(oc.t_end)) + ")");
+      cs[b].nfe += k;
+    };
+    const dim3 sgrid(egrid, B), rgrid(ODE_NBLK, B);
+    std::vector<char> active(B, 1);
+
+    // f0 = f(t0, y0): every selector is 0, the state of the whole batch is sx_
+    for (int b = 0; b < B; ++b) count(b, 1);
+    std::fill(table.begin(), table.end(), 0.0);
+    for (int b = 0; b < B; ++b) times[b] = oc.t_end;
+    upload(1, active);
+    evaluate(sx_);
+    { OdeEachArgs e = base_args(); e.kout_sel = 0; e.a.self = 0; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
+
+    if (oc.first_step > 0) {
+      for (int b = 0; b < B; ++b) cs[b].h_abs = oc.first_step;
+    } else {      // select_initial_step, per utterance: the probe evaluation at the utterance's own t0 + h0
+      for (int b = 0; b < B; ++b) count(b, 1);
+      { OdeEachArgs e = base_args(); e.d2 = 0; DRT_LAUNCH(ode_init_norms_each_kernel, rgrid, dim3(256), stream_, e); }
+      read_sums();
+      std::fill(table.begin(), table.end(), 0.0);
+      for (int b = 0; b < B; ++b) {
+        const double h0 = cs[b].probe_step(ode_ehost_[b * ODE_NSUM], ode_ehost_[b * ODE_NSUM + 1]);
+        table[((size_t)b * ODE_ROWS + 6) * ODE_STRIDE + 1] = h0 * cs[b].dir;
+        times[b] = cs[b].t + h0 * cs[b].dir;
+      }
+      upload(1, active);
+      { OdeEachArgs e = base_args(); e.a.row = 6; e.a.nterms = 1; e.a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
+      evaluate(ode_xs_);
+      { OdeEachArgs e = base_args(); e.a.xs = (const float*)ode_xs_; e.kout_sel = 6; e.a.self = 6; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
+      { OdeEachArgs e = base_args(); e.d2 = 1; DRT_LAUNCH(ode_init_norms_each_kernel, rgrid, dim3(256), stream_, e); }
+      read_sums();
+      for (int b = 0; b < B; ++b) cs[b].first_step_from_probe(ode_ehost_[b * ODE_NSUM + 1]);
+    }
+
+    for (;;) {
+      int nactive = 0;
+      for (int b = 0; b < B; ++b) { active[b] = cs[b].done() ? 0 : 1; nactive += active[b]; }
+      if (!nactive) break;
+      // ---- one round: an attempted step of every unfinished utterance; six batch evaluations, B scalars back
+      std::fill(table.begin(), table.end(), 0.0);
+      for (int b = 0; b < B; ++b) {
+        if (!active[b]) { for (int e = 0; e < 6; ++e) times[(size_t)e * B + b] = cs[b].t; continue; }      // (frozen: any valid time)
+        SG_REQUIRE(cs[b].begin_attempt(), "ode_sample_each: utterance " + std::to_string(b) + ": required step size is less than spacing between numbers (t = " +
+                   std::to_string(cs[b].t) + ")");
+        count(b, 6);
+        double tm[6];
+        cs[b].fill_attempt(tm, &table[(size_t)b * ODE_ROWS * ODE_STRIDE], ODE_STRIDE);
+        for (int e = 0; e < 6; ++e) times[(size_t)e * B + b] = tm[e];
+      }
+      ++ode_rounds_; ode_wasted_ += 6 * (B - nactive);
+      upload(6, active);
+      { OdeEachArgs e = base_args(); e.a.row = 6; e.a.nterms = 1; e.a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
+      for (int st = 0; st < 5; ++st) {
+        evaluate(ode_xs_);
+        OdeEachArgs e = base_args();
+        e.a.xs = (const float*)ode_xs_; e.a.kout = (float*)ode_k_[st + 1]; e.a.self = st + 1; e.a.nterms = st + 2;
+        e.a.xnext = (float*)ode_xs_;              // (in place: each thread reads its elements before it writes them)
+        e.to_new_state = st == 4 ? 1 : 0;         // y_new: to the stage-input buffer for the network AND to the utterance's other state buffer
+        DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e);
+        DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
+      }
+      evaluate(ode_xs_);
+      { OdeEachArgs e = base_args(); DRT_LAUNCH(ode_error_each_kernel, rgrid, dim3(256), stream_, e); }
+      read_sums();
+      for (int b = 0; b < B; ++b)
+        if (active[b] && cs[b].finish_attempt(ode_ehost_[b * ODE_NSUM])) sel[b] ^= 1;      // first same as last
+    }
+    for (int b = 0; b < B; ++b) {
+      const size_t off = ragged() ? ((size_t)F * rag_prefix(b)) : (size_t)b * F * T, len = (size_t)npix[b];
+      SG_CHECK(drt::memcpy_d2d(out + off, (sel[b] ? sxm_ : sx_) + off, len * 8, stream_));
+    }
+  }
+  // utterance b of the last ode_sample_each run
+  void ode_stats_each(int b, int* nfe, int* accepted, int* rejected, double* t_accepted, int cap, int* rounds, int* wasted) const {
+    SG_REQUIRE(b >= 0 && b < (int)ode_each_.size(), "ode_stats_each: no such utterance in the last run");
+    const OdeControl& c = ode_each_[b];
+    if (nfe) *nfe = c.nfe;
+    if (accepted) *accepted = c.n_accepted;
+    if (rejected) *rejected = c.n_rejected;
+    for (int i = 0; t_accepted && i < cap && i < (int)c.t_accepted.size(); ++i) t_accepted[i] = c.t_accepted[i];
+    if (rounds) *rounds = ode_rounds_;
+    if (wasted) *wasted = ode_wasted_;
+  }
+  size_t rag_prefix(int b) const { size_t s = 0; for (int i = 0; i < b; ++i) s += (size_t)rag_T_[i]; return s; }      // frames before utterance b
   void ode_stats(int* accepted, int* rejected, double* t_accepted, int cap) const {
     if (accepted) *accepted = ode_accepted_;
     if (rejected) *rejected = ode_rejected_;
@@ -2174,6 +2347,10 @@ class Engine {
   float2* ode_k_[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float2* ode_xs_ = nullptr; size_t ode_n_ = 0;
   double *ode_table_ = nullptr, *ode_partial_ = nullptr, *ode_result_ = nullptr, *ode_host_ = nullptr;
   int ode_accepted_ = 0, ode_rejected_ = 0; std::vector<double> ode_t_acc_;
+  // per-utterance step control (ode_sample_each): table, reduction buffers and the pinned results for ode_each_cap_ utterances; last run's controllers
+  static constexpr int kOdeEachMaxB = 1024;
+  double *ode_etable_ = nullptr, *ode_epartial_ = nullptr, *ode_eresult_ = nullptr, *ode_ehost_ = nullptr; int ode_each_cap_ = 0;
+  std::vector<OdeControl> ode_each_; int ode_rounds_ = 0, ode_wasted_ = 0;
   bool prof_ = false; std::vector<ProfRec> prof_recs_; size_t prof_used_ = 0; float prof_ms_[TC_COUNT]; double prof_flops_[TC_COUNT]; int prof_n_[TC_COUNT];
 };
 

@@ -46,15 +46,19 @@ struct OdeArgs {
 
 __device__ __forceinline__ float ode_drift1(float theta, float g2h, float y, float x, float s) { return fmaf(-g2h, s, theta * (y - x)); }
 
-// Fused drift + next stage: K_self = f(xs, t_row) from the score the network just left, xnext = x + sum_j c_j K_j.
-__global__ __launch_bounds__(256) void ode_stage_kernel(OdeArgs p) {
-  const double* row = p.table + (size_t)(p.row >= 0 ? p.row : *p.step_ptr) * ODE_STRIDE;
+// The passes below are written once, as bodies over one contiguous range of p.nfl floats that workgroup `blk` of `nblk` works on: the
+// batch-wide kernels (one range: the whole batch) and the per-utterance kernels (kernels_ode_each.h: one range per utterance, `blk`
+// and `nblk` counted inside the utterance) instantiate the same arithmetic, element order and summation order.
+
+// Fused drift + next stage: K_self = f(xs, t_row) from the score the network just left, xnext = x + sum_j c_j K_j
+// (xnext2: a second copy of xnext, or null).
+__device__ __forceinline__ void ode_stage_body(const OdeArgs& p, const double* row, float* xnext2, unsigned blk, unsigned nblk) {
   const float g2h = (float)row[0];
   double c[7];
 #pragma unroll
   for (int j = 0; j < 7; ++j) c[j] = j < p.nterms ? row[1 + j] : 0.0;
   const long long nq = p.nfl >> 2;
-  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long long)gridDim.x * 256) {
+  for (long long q = (long long)blk * 256 + threadIdx.x; q < nq; q += (long long)nblk * 256) {
     float kv[4] = {0.f, 0.f, 0.f, 0.f};
     if (p.kout) {
       const float4 xs = reinterpret_cast<const float4*>(p.xs)[q], yv = reinterpret_cast<const float4*>(p.y)[q];
@@ -74,32 +78,39 @@ __global__ __launch_bounds__(256) void ode_stage_kernel(OdeArgs p) {
       acc[0] += c[j] * (double)kj.x; acc[1] += c[j] * (double)kj.y; acc[2] += c[j] * (double)kj.z; acc[3] += c[j] * (double)kj.w;
     }
     const float4 xv = reinterpret_cast<const float4*>(p.x)[q];
-    reinterpret_cast<float4*>(p.xnext)[q] = make_float4((float)((double)xv.x + acc[0]), (float)((double)xv.y + acc[1]),
-                                                        (float)((double)xv.z + acc[2]), (float)((double)xv.w + acc[3]));
+    const float4 xo = make_float4((float)((double)xv.x + acc[0]), (float)((double)xv.y + acc[1]),
+                                  (float)((double)xv.z + acc[2]), (float)((double)xv.w + acc[3]));
+    reinterpret_cast<float4*>(p.xnext)[q] = xo;
+    if (xnext2) reinterpret_cast<float4*>(xnext2)[q] = xo;
   }
   // tail: one complex element when n is odd
-  if ((p.nfl & 3) && blockIdx.x == 0 && threadIdx.x < (unsigned)(p.nfl & 3)) {
+  if ((p.nfl & 3) && blk == 0 && threadIdx.x < (unsigned)(p.nfl & 3)) {
     const long long i = (nq << 2) + threadIdx.x;
     float kv = 0.f;
     if (p.kout) { kv = ode_drift1(p.theta, g2h, p.y[i], p.xs[i], p.score[i]); p.kout[i] = kv; }
     if (p.xnext) {
       double acc = 0.0;
       for (int j = 0; j < p.nterms; ++j) if (c[j] != 0.0) acc += c[j] * (double)((p.kout && j == p.self) ? kv : p.k[j][i]);
-      p.xnext[i] = (float)((double)p.x[i] + acc);
+      const float xo = (float)((double)p.x[i] + acc);
+      p.xnext[i] = xo;
+      if (xnext2) xnext2[i] = xo;
     }
   }
 }
+__global__ __launch_bounds__(256) void ode_stage_kernel(OdeArgs p) {
+  ode_stage_body(p, p.table + (size_t)(p.row >= 0 ? p.row : *p.step_ptr) * ODE_STRIDE, nullptr, blockIdx.x, gridDim.x);
+}
 
 // block-level sum of ODE_NSUM doubles in a fixed order: butterfly inside the wave, the four waves in sequence
-__device__ __forceinline__ void ode_block_sums(double s0, double s1, double* partial) {
+__device__ __forceinline__ void ode_block_sums(double s0, double s1, double* partial, unsigned blk) {
   __shared__ double s_w[4 * ODE_NSUM];
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) { s0 += drt_shfl_xor_f64(s0, m); s1 += drt_shfl_xor_f64(s1, m); }
   if ((threadIdx.x & 63) == 0) { s_w[(threadIdx.x >> 6) * ODE_NSUM] = s0; s_w[(threadIdx.x >> 6) * ODE_NSUM + 1] = s1; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    partial[(size_t)blockIdx.x * ODE_NSUM] = (s_w[0] + s_w[2]) + (s_w[4] + s_w[6]);
-    partial[(size_t)blockIdx.x * ODE_NSUM + 1] = (s_w[1] + s_w[3]) + (s_w[5] + s_w[7]);
+    partial[(size_t)blk * ODE_NSUM] = (s_w[0] + s_w[2]) + (s_w[4] + s_w[6]);
+    partial[(size_t)blk * ODE_NSUM + 1] = (s_w[1] + s_w[3]) + (s_w[5] + s_w[7]);
   }
 }
 
@@ -107,15 +118,14 @@ __device__ __forceinline__ double ode_abs(double re, double im) { return sqrt(re
 
 // Last pass of an attempted step: K_6 = f(y_new, t + h) from the score at y_new, err = sum_j (h E_j) K_j,
 // scale = atol + max(|x|, |y_new|) rtol, partial sums of |err / scale|^2 over complex elements (sum 0; sum 1 = 0).
-__global__ __launch_bounds__(256) void ode_error_kernel(OdeArgs p) {
-  const double* row = p.table + (size_t)(p.row >= 0 ? p.row : *p.step_ptr) * ODE_STRIDE;
+__device__ __forceinline__ void ode_error_body(const OdeArgs& p, const double* row, unsigned blk, unsigned nblk) {
   const float g2h = (float)row[0];
   double c[7];
 #pragma unroll
   for (int j = 0; j < 7; ++j) c[j] = row[1 + j];
   const long long npair = p.nfl >> 2, nc = p.nfl >> 1;      // 16-byte items (two complex elements), complex elements
   double sum = 0.0;
-  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < npair; q += (long long)gridDim.x * 256) {
+  for (long long q = (long long)blk * 256 + threadIdx.x; q < npair; q += (long long)nblk * 256) {
     const float4 xn = reinterpret_cast<const float4*>(p.xnew)[q], yv = reinterpret_cast<const float4*>(p.y)[q];
     const float4 sv = reinterpret_cast<const float4*>(p.score)[q], xv = reinterpret_cast<const float4*>(p.x)[q];
     const float k6[4] = {ode_drift1(p.theta, g2h, yv.x, xn.x, sv.x), ode_drift1(p.theta, g2h, yv.y, xn.y, sv.y),
@@ -132,7 +142,7 @@ __global__ __launch_bounds__(256) void ode_error_kernel(OdeArgs p) {
     const double sb = p.atol + fmax(ode_abs(xv.z, xv.w), ode_abs(xn.z, xn.w)) * p.rtol;
     sum += (e[0] * e[0] + e[1] * e[1]) / (sa * sa) + (e[2] * e[2] + e[3] * e[3]) / (sb * sb);
   }
-  if ((nc & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
+  if ((nc & 1) && blk == 0 && threadIdx.x == 0) {
     const long long i = npair << 2;
     double e[2];
     for (int r = 0; r < 2; ++r) {
@@ -144,18 +154,21 @@ __global__ __launch_bounds__(256) void ode_error_kernel(OdeArgs p) {
     const double s = p.atol + fmax(ode_abs(p.x[i], p.x[i + 1]), ode_abs(p.xnew[i], p.xnew[i + 1])) * p.rtol;
     sum += (e[0] * e[0] + e[1] * e[1]) / (s * s);
   }
-  ode_block_sums(sum, 0.0, p.partial);
+  ode_block_sums(sum, 0.0, p.partial, blk);
+}
+__global__ __launch_bounds__(256) void ode_error_kernel(OdeArgs p) {
+  ode_error_body(p, p.table + (size_t)(p.row >= 0 ? p.row : *p.step_ptr) * ODE_STRIDE, blockIdx.x, gridDim.x);
 }
 
 // The norms of the initial-step rule with scale = atol + |x| rtol:
 //   sum 0 = sum |x / scale|^2 (d0; skipped when k[1] is given),  sum 1 = sum |(k[0] - k[1]) / scale|^2  (d1: k[1] null; d2: k[1] = K_0)
-__global__ __launch_bounds__(256) void ode_init_norms_kernel(OdeArgs p) {
+__device__ __forceinline__ void ode_init_norms_body(const OdeArgs& p, unsigned blk, unsigned nblk) {
   const long long nc = p.nfl >> 1;
   const float2* x = reinterpret_cast<const float2*>(p.x);
   const float2* a = reinterpret_cast<const float2*>(p.k[0]);
   const float2* b = reinterpret_cast<const float2*>(p.k[1]);
   double s0 = 0.0, s1 = 0.0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < nc; i += (long long)gridDim.x * 256) {
+  for (long long i = (long long)blk * 256 + threadIdx.x; i < nc; i += (long long)nblk * 256) {
     const float2 xv = x[i], av = a[i];
     const double sc = p.atol + ode_abs(xv.x, xv.y) * p.rtol;
     double dr = av.x, di = av.y;
@@ -163,16 +176,18 @@ __global__ __launch_bounds__(256) void ode_init_norms_kernel(OdeArgs p) {
     else s0 += ((double)xv.x * xv.x + (double)xv.y * xv.y) / (sc * sc);
     s1 += (dr * dr + di * di) / (sc * sc);
   }
-  ode_block_sums(s0, s1, p.partial);
+  ode_block_sums(s0, s1, p.partial, blk);
 }
+__global__ __launch_bounds__(256) void ode_init_norms_kernel(OdeArgs p) { ode_init_norms_body(p, blockIdx.x, gridDim.x); }
 
 // second stage of every reduction: one wave adds the ODE_NBLK partial sums in a fixed order
-__global__ __launch_bounds__(64) void ode_reduce_final_kernel(const double* partial, double* result) {
+__device__ __forceinline__ void ode_reduce_final_body(const double* partial, double* result) {
   double s0 = 0.0, s1 = 0.0;
   for (int k = threadIdx.x; k < ODE_NBLK; k += 64) { s0 += partial[(size_t)k * ODE_NSUM]; s1 += partial[(size_t)k * ODE_NSUM + 1]; }
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) { s0 += drt_shfl_xor_f64(s0, m); s1 += drt_shfl_xor_f64(s1, m); }
   if (threadIdx.x == 0) { result[0] = s0; result[1] = s1; }
 }
+__global__ __launch_bounds__(64) void ode_reduce_final_kernel(const double* partial, double* result) { ode_reduce_final_body(partial, result); }
 
 }  // namespace sgmse

@@ -102,10 +102,13 @@ def build_sampler(model: ScoreModel, Y: torch.Tensor, args, seed=None, streams=N
         if args.sampler_type == "ode":
             solver = getattr(args, "ode_solver", None)
             if solver is not None:      # the reference's adaptive RK45 sampler (rectangular batches only); 'native': as one library call
-                if isinstance(Y, (list, tuple)):
+                each = solver == "native" and getattr(args, "ode_step_control", None) == "utterance"      # one step control per utterance
+                if isinstance(Y, (list, tuple)) and not each:
                     raise TypeError(f"--ode_solver {solver} integrates one rectangular batch (its error norm couples the utterances): "
                                     f"got a ragged list of {len(Y)} spectrograms; run without --ragged")
                 extra = dict(seed=seed, streams=streams) if solver == "native" else {}
+                if each:
+                    extra["step_control"] = "utterance"
                 return model.get_ode_sampler(Y, adaptive=True, denoise=False, solver=solver, **extra)
             return model.get_ode_sampler(Y, N=args.N, seed=seed, streams=streams)
         raise ValueError(f"Sampler type {args.sampler_type} not supported")
@@ -295,10 +298,12 @@ def enhance_files(model: ScoreModel, files: List[str], test_dir: str, enhanced_d
         warnings.warn("--ragged needs an OUVE model and the 'ald' / 'none' corrector (the Langevin corrector couples the utterances of "
                       "a batch; the Schroedinger-bridge sampler is not built for it): batching by padded length instead")
         ragged = False
-    if ragged and args.sampler_type == "ode" and getattr(args, "ode_solver", None) is not None:
+    ode_each = getattr(args, "ode_solver", None) == "native" and getattr(args, "ode_step_control", None) == "utterance"
+    if ragged and args.sampler_type == "ode" and getattr(args, "ode_solver", None) is not None and not ode_each:
         import warnings
         warnings.warn("--ragged does not combine with --ode_solver: the adaptive solver's one error norm couples the utterances of a "
-                      "batch, so it integrates rectangular batches only: batching by padded length instead")
+                      "batch, so it integrates rectangular batches only: batching by padded length instead "
+                      "(--ode_solver native --ode_step_control utterance integrates every utterance on its own and keeps --ragged)")
         ragged = False
     batches = plan_batches(list(range(n)), frames, args.batch_size, ragged)
     on_gpu = device.type == "cuda"
@@ -401,6 +406,10 @@ def main(argv=None) -> int:
     parser.add_argument("--ode_solver", type=str, choices=("scipy", "native"), default=None,
                         help="With --sampler_type ode: the reference's adaptive RK45 probability-flow sampler instead of the fixed-step loop, "
                              "driven by scipy through host memory ('scipy') or as one HIP library call ('native')")
+    parser.add_argument("--ode_step_control", type=str, choices=("batch", "utterance"), default="batch",
+                        help="With --ode_solver native: 'batch' = one error norm and one step sequence for the whole batch, as scipy sees the "
+                             "flattened state; 'utterance' = every file gets its own step control, as in a one-file-at-a-time run (an enhanced "
+                             "file then does not depend on what shares its batch, and --ragged stays on)")
     parser.add_argument("--corrector", type=str, choices=("ald", "langevin", "none"), default="ald", help="Corrector class for the PC sampler.")
     parser.add_argument("--corrector_steps", type=int, default=1, help="Number of corrector steps")
     parser.add_argument("--snr", type=float, default=0.5, help="SNR value for (annealed) Langevin dynmaics")

@@ -268,7 +268,8 @@ class ScoreModel(nn.Module):
         """reference model.py:370-390.  ``denoise=False`` (the only setting under which the reference's function completes) selects the
         reference's adaptive scipy solver -- host round trips, ``seed`` / ``use_graph`` / ``streams`` / ``N`` do not apply (a warning says
         so); with ``solver="native"`` the same RK45 solver runs as one library call without host round trips, and ``seed`` / ``streams`` /
-        ``noise`` / ``z`` apply (``N`` and ``use_graph`` still do not).  The default runs the fused fixed-step probability-flow loop.
+        ``noise`` / ``z`` apply (``N`` and ``use_graph`` still do not); ``step_control="utterance"`` then gives every utterance its own step
+        control (``y`` may be a ragged list; see sampling.get_ode_sampler).  The default runs the fused fixed-step probability-flow loop.
         ``adaptive=True/False`` chooses explicitly (sampling.get_ode_sampler)."""
         sde = self.sde.copy()
         sde.N = self.sde.N if N is None else N

@@ -141,12 +141,18 @@ def _adaptive_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol,
     return ode_sampler
 
 
-def _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, method, eps, device, noise, seed, streams, solver_kwargs):
+def _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, method, eps, device, noise, seed, streams, solver_kwargs,
+                        step_control="batch"):
     """The same solver as ``_adaptive_ode_sampler`` -- scipy's RK45 (Dormand-Prince 5(4)) with its initial-step rule and step control
     over the flattened batch -- as ONE library call (sgmse_ode_sample): state, stage slopes and error estimate stay on the device, the
-    host reads one scalar (the error norm) per attempted step.  Nothing here falls back: what the library call cannot do raises."""
-    if isinstance(y, (list, tuple)):
-        raise TypeError("the adaptive ODE sampler integrates one rectangular batch: pass a tensor, not a ragged list")
+    host reads one scalar (the error norm) per attempted step.  Nothing here falls back: what the library call cannot do raises.
+    ``step_control="utterance"`` (sgmse_ode_sample_each): one controller per utterance, so ``y`` may be a ragged list, an utterance's
+    result is that of its own single-utterance run, and the returned nfe is the largest utterance's."""
+    ragged = isinstance(y, (list, tuple))
+    if ragged and step_control != "utterance":
+        raise TypeError("the adaptive ODE sampler integrates one rectangular batch: pass a tensor, not a ragged list "
+                        "(step_control='utterance' integrates every utterance on its own and takes one)")
+    y0 = y[0] if ragged else y
     unsupported = []
     if not isinstance(sde, OUVESDE):
         unsupported.append(f"sde={type(sde).__name__} (only OUVESDE)")
@@ -156,7 +162,7 @@ def _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, m
     dnn = getattr(score_fn, "dnn", None)
     if dnn is None or not hasattr(dnn, "engine") or getattr(score_fn, "_native_score_wrapper", False) is not True:
         unsupported.append("score_fn (needs a ScoreModel on a HIP backbone)")
-    if device is not None and torch.device(device).type != y.device.type:
+    if device is not None and torch.device(device).type != y0.device.type:
         unsupported.append(f"device={device!r} (the solver runs where y lives)")
     if unsupported:
         raise ValueError("get_ode_sampler(solver='native') does not support " + "; ".join(unsupported) + " -- use solver='scipy'")
@@ -166,9 +172,15 @@ def _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, m
     if max_step is not None and not max_step > 0:
         raise ValueError("`max_step` must be positive.")
     max_step = 0.0 if max_step is None or max_step == float("inf") else float(max_step)
-    ctx = dnn.engine(y.device)
+    ctx = dnn.engine(y0.device)
     std1 = float(sde._std(torch.ones(1))[0])
     affine_fn = score_fn.score_affine if score_fn.score_affine(torch.ones(1)) is not None else None
+    extra = dict(step_control=step_control) if step_control != "batch" else {}
+
+    def tail(x, yy):      # the extra predictor step of the scipy-driven path (see _adaptive_ode_sampler)
+        predictor = ReverseDiffusionPredictor(sde, score_fn, probability_flow=False)
+        vec_eps = torch.ones(x.shape[0], device=x.device) * eps
+        return predictor.update_fn(x, yy, vec_eps, torch.tensor(eps, device=x.device))[1]
 
     def ode_sampler(z=None, max_nfe=100000, **kw):
         s = seed if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -176,11 +188,15 @@ def _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, m
             x, nfe = ctx.ode_sample(y, theta=float(sde.theta), sigma_min=float(sde.sigma_min), sigma_max=float(sde.sigma_max), std1=std1,
                                     t_end=float(sde.T), eps=float(eps), rtol=float(rtol), atol=float(atol), first_step=float(first_step or 0.0),
                                     max_step=max_step, noise=None if z is not None else noise, x0=z, seed=s, streams=streams,
-                                    affine_fn=affine_fn, max_nfe=max_nfe)
-            if denoise:      # the extra predictor step of the scipy-driven path (see _adaptive_ode_sampler)
-                predictor = ReverseDiffusionPredictor(sde, score_fn, probability_flow=False)
-                vec_eps = torch.ones(x.shape[0], device=x.device) * eps
-                _, x = predictor.update_fn(x, y, vec_eps, torch.tensor(eps, device=x.device))
+                                    affine_fn=affine_fn, max_nfe=max_nfe, **extra)
+            if ragged:      # a list of [1,F,T_b]: the tail utterance by utterance
+                if denoise:
+                    x = [tail(xb[None], yb.reshape(1, 1, *yb.shape[-2:]))[0] for xb, yb in zip(x, y)]
+                if inverse_scaler is not None:
+                    x = [inverse_scaler(xb) for xb in x]
+                return x, nfe
+            if denoise:
+                x = tail(x, y)
             if inverse_scaler is not None:
                 x = inverse_scaler(x)
             return x, nfe
@@ -190,7 +206,7 @@ def _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, m
 
 def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e-5, atol=1e-5, method="RK45", eps=3e-2,
                     device=None, noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, use_graph: bool = True,
-                    streams=None, adaptive: Optional[bool] = None, solver: str = "scipy", **kwargs):
+                    streams=None, adaptive: Optional[bool] = None, solver: str = "scipy", step_control: str = "batch", **kwargs):
     """Probability-flow sampler (reference sampling/__init__.py:73-143), in two forms.
 
     ``adaptive=True`` -- the reference's own behaviour: scipy's black-box solver (``method``, ``rtol``, ``atol``, extra keyword
@@ -199,6 +215,9 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
     (RK45 with scipy's step control, one error norm over the whole batch) as one HIP library call without host round trips: it needs an
     OUVESDE, a ScoreModel on a HIP backbone and ``method="RK45"``, takes ``first_step`` / ``max_step`` of solve_ivp's keywords, and
     ``seed`` / ``streams`` / ``noise`` / ``z`` all apply; anything else raises ValueError.  The returned callable takes ``max_nfe``.
+    ``step_control="utterance"`` (native solver only, else ValueError) gives every utterance its own step control instead of the one
+    error norm over the batch: an utterance's result no longer depends on what shares its batch (it is, bit for bit, that of its
+    single-utterance run), ``y`` may be a ragged list, ``max_nfe`` caps each utterance and the returned nfe is the largest utterance's.
 
     ``adaptive=False`` -- the fixed-step counterpart on the sampler's own time grid (BASELINE configs[2]): N Euler
     steps of ``sde.reverse(score_fn, probability_flow=True).discretize`` (sdes.py:130-135), x <- x - rev_f, no noise, N NFE, as one
@@ -209,13 +228,19 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
     the adaptive solver and the default selects the fixed-step sampler."""
     if solver not in ("scipy", "native"):
         raise ValueError(f"solver must be 'scipy' or 'native', got {solver!r}")
+    if step_control not in ("batch", "utterance"):
+        raise ValueError(f"step_control must be 'batch' or 'utterance', got {step_control!r}")
+    if step_control == "utterance" and solver != "native":
+        raise ValueError("step_control='utterance' is the native solver's per-utterance mode: pass solver='native' (scipy integrates the "
+                         "flattened batch under one error norm)")
     if adaptive is None:
         adaptive = denoise is False
     if solver == "native":
         if not adaptive:
             raise ValueError("solver='native' selects the adaptive solver's implementation: pass adaptive=True (or denoise=False); the fixed-step "
                              "sampler (adaptive=False) always runs in the library")
-        return _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, method, eps, device, noise, seed, streams, kwargs)
+        return _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, method, eps, device, noise, seed, streams, kwargs,
+                                   step_control)
     if adaptive:
         dropped = [k for k, v in (("seed", seed), ("streams", streams)) if v is not None] + ([] if use_graph else ["use_graph"])
         if dropped:

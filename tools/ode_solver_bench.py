@@ -10,6 +10,11 @@ own run-to-run spread (max - min over its runs).  The native run of a pair goes 
 problem the solver cannot finish ends the row with a message before the uncapped scipy run starts.
 
     python tools/ode_solver_bench.py [--batches 32 1] [--tols 1e-3 1e-5] [--runs 3] [--seconds 4] [--out FILE.json]
+
+--step_control utterance measures the native solver's per-utterance step control (sgmse_ode_sample_each) instead: per (batch,
+tolerance) the wall time of the batched run against the same utterances integrated one by one with the existing B = 1 path (the two
+alternate, --runs each, in this process; utterances of different levels, priors from one seed and the utterance's stream id), the
+rounds, the utterance-evaluations wasted on finished utterances, and whether the outputs are byte-equal between the two (required).
 """
 import argparse
 import json
@@ -33,6 +38,7 @@ def main():
     ap.add_argument("--warmup-tol", type=float, default=1e-3)
     ap.add_argument("--max-nfe", type=int, default=3000)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--step_control", type=str, choices=("batch", "utterance"), default="batch")
     ap.add_argument("--test-emulator", type=str, default=None, metavar="LIB",
                     help="TEST ONLY: run this script's logic on CPU tensors with the workgroup-emulator build of the kernels; never a measurement")
     a = ap.parse_args()
@@ -53,6 +59,8 @@ def main():
     model = ScoreModel("ncsnpp", "ouve", nf=a.nf, theta=1.5, sigma_min=0.05, sigma_max=0.5)      # random init, seeded (as bench.py)
     model.to(dev).eval()
     rel = lambda p, q: float((p - q).norm() / q.norm())
+    if a.step_control == "utterance":
+        return each_rows(a, model, dev, sync, name)
     rows = []
     for B in a.batches:
         g = torch.Generator().manual_seed(1000)
@@ -115,6 +123,68 @@ def main():
         with open(a.out, "w") as fh:
             json.dump(res, fh, indent=1)
     if any("failed" in r or not r["native_no_worse_than_scipy"] for r in rows):
+        raise SystemExit(1)
+
+
+def each_rows(a, model, dev, sync, name):
+    """--step_control utterance: batched per-utterance step control against the one-by-one B = 1 runs."""
+    import torch
+    from sgmse_amd.util.other import pad_spec
+    rows = []
+    for B in a.batches:
+        g = torch.Generator().manual_seed(1000)
+        wav = torch.randn(B, int(a.seconds * 16000), generator=g)
+        level = torch.logspace(-1.5, 0, B)[torch.randperm(B, generator=g)]            # a corpus is not one level: the step sequences differ
+        wav = (wav / wav.abs().amax(dim=1, keepdim=True) * level[:, None]).to(dev)
+        Y = pad_spec(model._forward_transform(model._stft(wav)).unsqueeze(1), mode="zero_pad")
+        ids = list(range(B))
+
+        def batched(tol):
+            sync()
+            t0 = time.perf_counter()
+            out, nfe = model.get_ode_sampler(Y, denoise=False, rtol=tol, atol=tol, solver="native", step_control="utterance", seed=7,
+                                             streams=ids)(max_nfe=a.max_nfe)
+            sync()
+            return out, nfe, time.perf_counter() - t0
+
+        def one_by_one(tol):
+            sync()
+            t0 = time.perf_counter()
+            outs, nfes = [], []
+            for b in range(B):
+                o, n = model.get_ode_sampler(Y[b:b + 1], denoise=False, rtol=tol, atol=tol, solver="native", seed=7, streams=[ids[b]])(max_nfe=a.max_nfe)
+                outs.append(o)
+                nfes.append(n)
+            sync()
+            return torch.cat(outs), nfes, time.perf_counter() - t0
+        batched(a.warmup_tol)
+        model.get_ode_sampler(Y[:1], denoise=False, rtol=a.warmup_tol, atol=a.warmup_tol, solver="native", seed=7, streams=[0])()
+        for tol in a.tols:
+            rec = dict(batch=B, shape=list(Y.shape), rtol=tol, atol=tol, batched_seconds=[], one_by_one_seconds=[])
+            for _ in range(a.runs):
+                out_b, nfe, sec = batched(tol)
+                st = model.dnn.engine(dev).ode_stats_each()
+                rec["batched_seconds"].append(sec)
+                out_1, nfes, sec1 = one_by_one(tol)
+                rec["one_by_one_seconds"].append(sec1)
+                print(f"  batch {B} rtol=atol={tol:g}: batched {sec:.2f} s ({nfe} batch evaluations), one by one {sec1:.2f} s", flush=True)
+            per = [u["nfe"] for u in st["utterances"]]
+            mb, m1 = statistics.median(rec["batched_seconds"]), statistics.median(rec["one_by_one_seconds"])
+            rec.update(batch_evaluations=nfe, rounds=st["rounds"], wasted_utterance_evaluations=st["wasted"],
+                       wasted_share=st["wasted"] / float(B * nfe), nfe_per_utterance=per, nfe_one_by_one=nfes,
+                       byte_equal=bool(torch.equal(out_b, out_1)) and per == nfes, batched_median_seconds=mb, one_by_one_median_seconds=m1,
+                       speedup=m1 / mb, utterances_per_second_batched=B / mb, utterances_per_second_one_by_one=B / m1)
+            rows.append(rec)
+            print(f"batch {B} {tuple(Y.shape)} rtol=atol={tol:g}: batched {mb:.2f} s, one by one {m1:.2f} s, speed-up {rec['speedup']:.2f}x; "
+                  f"rounds {st['rounds']}, nfe per utterance {min(per)}..{max(per)}, wasted {st['wasted']} of {B * nfe} utterance-evaluations "
+                  f"({100 * rec['wasted_share']:.1f} %); byte-equal: {rec['byte_equal']}", flush=True)
+    res = dict(device=name, nf=a.nf, runs=a.runs, seconds=a.seconds, step_control="utterance", rows=rows)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+    if not all(r["byte_equal"] for r in rows):
         raise SystemExit(1)
 
 
