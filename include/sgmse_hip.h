@@ -135,7 +135,8 @@ typedef struct sgmse_ode_cfg {
 int sgmse_ode_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int T, const sgmse_ode_cfg* cfg, const void* noise,
                      const void* x0, unsigned long long seed, int* nfe);
 /* the last sgmse_ode_sample run of this context: accepted and rejected step counts and the first min(cap, accepted) accepted time
- * points (the last one is eps exactly after a completed run).  Any of the pointers may be NULL. */
+ * points (the last one is eps exactly after a completed run).  Any of the pointers may be NULL.  The two samplers keep one set of
+ * statistics: after a sgmse_ode_sample_each run this reports that run's utterance 0. */
 int sgmse_ode_stats(sgmse_ctx* ctx, int* accepted, int* rejected, double* t_accepted, int cap);
 /* -- the same solver with PER-UTTERANCE step control: every utterance of the batch is integrated as if it were alone -- its own
  *    initial step, stage times, error norm (over its own F*T_b elements), accept / reject decisions, step count and end of
@@ -157,7 +158,8 @@ int sgmse_ode_sample_each(sgmse_ctx* ctx, const void* Y, void* out, int B, int F
                           const void* x0, unsigned long long seed, int* nfe_max);
 /* utterance b of the last sgmse_ode_sample_each run of this context: its evaluation count, accepted and rejected step counts and the
  * first min(cap, accepted) accepted time points; and of the run as a whole: *rounds, and *wasted = the utterance-evaluations spent on
- * slots of utterances that had already finished (6 per finished utterance and round; B * *nfe_max is the total).  Any pointer may be NULL. */
+ * slots of utterances that had already finished (6 per finished utterance and round; B * *nfe_max is the total).  Any pointer may be NULL.
+ * After a sgmse_ode_sample run the one "utterance", b = 0, is that run's whole batch. */
 int sgmse_ode_stats_each(sgmse_ctx* ctx, int b, int* nfe, int* accepted, int* rejected, double* t_accepted, int cap, int* rounds,
                          int* wasted);
 

@@ -421,13 +421,20 @@ class Context:
         the returned nfe is the largest utterance's, and ``ode_stats_each`` describes the run."""
         if step_control not in ("batch", "utterance"):
             raise ValueError(f"step_control must be 'batch' or 'utterance', got {step_control!r}")
+        values = dict(theta=theta, sigma_min=sigma_min, sigma_max=sigma_max, std1=std1, t_end=t_end, eps=eps, rtol=rtol, atol=atol,
+                      first_step=first_step, max_step=max_step, max_nfe=max_nfe)
         if step_control == "utterance":
-            return self._ode_sample_each(Y, dict(theta=theta, sigma_min=sigma_min, sigma_max=sigma_max, std1=std1, t_end=t_end, eps=eps,
-                                                 rtol=rtol, atol=atol, first_step=first_step, max_step=max_step, max_nfe=max_nfe),
-                                         noise, x0, seed, streams, affine_fn)
+            return self._ode_sample_each(Y, values, noise, x0, seed, streams, affine_fn)
         if isinstance(Y, (list, tuple)):
             raise TypeError("the adaptive ODE sampler integrates one rectangular batch (its error norm couples the utterances): "
                             "pass a tensor, not a ragged list")
+        Y, noise, x0 = self._ode_rect_inputs(Y, noise, x0)
+        # as in forward / pc_sample / sb_sample: a frame table left in force by an earlier ragged call is no request of this caller's
+        # (a ragged batch is a list, refused above); a uniform call switches it off
+        return self._ode_call(self.lib.sgmse_ode_sample, Y, Y.shape[0], Y.shape[2], Y.shape[3], [], 1, values, noise, x0, seed, streams, affine_fn)
+
+    def _ode_rect_inputs(self, Y, noise, x0):
+        """y [B,1,F,T] and the replayed noise or the start state of a rectangular batch, checked: (y, noise, x0)."""
         Y = check_tensor(Y, "y", torch.complex64, self.device)
         if Y.dim() != 4 or Y.shape[1] != 1:
             raise ValueError(f"expected y of shape [B,1,F,T], got {tuple(Y.shape)}")
@@ -444,8 +451,13 @@ class Context:
             x0 = check_tensor(x0, "z", torch.complex64, self.device)
             if tuple(x0.shape) != tuple(Y.shape):
                 raise ValueError(f"the start state must have y's shape {tuple(Y.shape)}, got {tuple(x0.shape)}")
-        cfg, failure, cb = self._ode_cfg(dict(theta=theta, sigma_min=sigma_min, sigma_max=sigma_max, std1=std1, t_end=t_end, eps=eps, rtol=rtol,
-                                              atol=atol, first_step=first_step, max_step=max_step, max_nfe=max_nfe), affine_fn)
+        return Y, noise, x0
+
+    def _ode_call(self, fn, Y, B, F_, T, frames, groups, values, noise, x0, seed, streams, affine_fn):
+        """One sgmse_ode_sample / sgmse_ode_sample_each call over checked inputs (``frames``: the ragged batch's frame table, [] for
+        a rectangular one; ``groups``: controllers of the run, what ode_stats_each will list): (out, nfe).  An exception of the host
+        callback is raised again here; a failed run raises RuntimeError."""
+        cfg, failure, cb = self._ode_cfg(values, affine_fn)
         if streams is not None:
             if len(streams) != B:
                 raise ValueError(f"streams must name the {B} utterances of the batch, got {len(streams)}")
@@ -453,14 +465,12 @@ class Context:
         out = torch.empty_like(Y)
         nfe = _I(0)
         self.use_current_stream()
-        # as in forward / pc_sample / sb_sample: a frame table left in force by an earlier ragged call is no request of this caller's
-        # (a ragged batch is a list, refused above); a uniform call switches it off
-        self.set_frames([])
-        rc = self.lib.sgmse_ode_sample(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, C.byref(cfg), ptr(noise), ptr(x0),
-                                       C.c_ulonglong(seed & (2 ** 64 - 1)), C.byref(nfe))
+        self.set_frames(frames)
+        rc = fn(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, C.byref(cfg), ptr(noise), ptr(x0), C.c_ulonglong(seed & (2 ** 64 - 1)), C.byref(nfe))
         if failure:
             raise failure[0]
         self.check(rc)
+        self._ode_each_B = groups
         return out, nfe.value
 
     @staticmethod
@@ -489,56 +499,25 @@ class Context:
 
     def _ode_sample_each(self, Y, values, noise, x0, seed, streams, affine_fn):
         """``ode_sample(step_control="utterance")``: sgmse_ode_sample_each over a tensor [B,1,F,T] or a ragged list."""
-        frames = None
-        if isinstance(Y, (list, tuple)):
-            if noise is not None:
-                raise ValueError("ragged batches take the prior from seed / streams or a start state z, not from replayed noise")
-            frames, F_ = _ragged_geometry(Y, 1, "y")
-            B, T = len(Y), max(frames)
-            Y = torch.cat([check_tensor(y, "y", torch.complex64, self.device).reshape(-1) for y in Y])
-            if x0 is not None:
-                if not isinstance(x0, (list, tuple)) or len(x0) != B or _ragged_geometry(x0, 1, "z") != (frames, F_):
-                    raise ValueError("the start state of a ragged batch is a list with the shapes of y's utterances")
-                x0 = torch.cat([check_tensor(x, "z", torch.complex64, self.device).reshape(-1) for x in x0])
-        else:
-            Y = check_tensor(Y, "y", torch.complex64, self.device)
-            if Y.dim() != 4 or Y.shape[1] != 1:
-                raise ValueError(f"expected y of shape [B,1,F,T], got {tuple(Y.shape)}")
+        if not isinstance(Y, (list, tuple)):
+            Y, noise, x0 = self._ode_rect_inputs(Y, noise, x0)
             B, _, F_, T = Y.shape
-            if noise is not None and x0 is not None:
-                raise ValueError("give replayed noise or a start state, not both")
-            if noise is not None:
-                noise = check_tensor(noise, "noise", torch.complex64, self.device)
-                if noise.dim() == Y.dim() + 1:
-                    noise = noise[0].contiguous()
-                if tuple(noise.shape) != tuple(Y.shape):
-                    raise ValueError(f"noise must be [{B},1,{F_},{T}] complex64 (or [ndraws,{B},1,{F_},{T}]), got {tuple(noise.shape)}")
-            if x0 is not None:
-                x0 = check_tensor(x0, "z", torch.complex64, self.device)
-                if tuple(x0.shape) != tuple(Y.shape):
-                    raise ValueError(f"the start state must have y's shape {tuple(Y.shape)}, got {tuple(x0.shape)}")
-        cfg, failure, cb = self._ode_cfg(values, affine_fn)
-        if streams is not None:
-            if len(streams) != B:
-                raise ValueError(f"streams must name the {B} utterances of the batch, got {len(streams)}")
-            self.set_noise_streams(streams)
-        out = torch.empty_like(Y)
-        nfe = _I(0)
-        self.use_current_stream()
-        self.set_frames(frames if frames is not None else [])
-        rc = self.lib.sgmse_ode_sample_each(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, C.byref(cfg), ptr(noise), ptr(x0),
-                                            C.c_ulonglong(seed & (2 ** 64 - 1)), C.byref(nfe))
-        if failure:
-            raise failure[0]
-        self.check(rc)
-        self._ode_each_B = B
-        if frames is not None:                  # unpack: one [1,F,T_b] tensor per utterance
-            outs, o = [], 0
-            for T_b in frames:
-                outs.append(out[o:o + F_ * T_b].reshape(1, F_, T_b))
-                o += F_ * T_b
-            return outs, nfe.value
-        return out, nfe.value
+            return self._ode_call(self.lib.sgmse_ode_sample_each, Y, B, F_, T, [], B, values, noise, x0, seed, streams, affine_fn)
+        if noise is not None:
+            raise ValueError("ragged batches take the prior from seed / streams or a start state z, not from replayed noise")
+        frames, F_ = _ragged_geometry(Y, 1, "y")
+        B, T = len(Y), max(frames)
+        Y = torch.cat([check_tensor(y, "y", torch.complex64, self.device).reshape(-1) for y in Y])
+        if x0 is not None:
+            if not isinstance(x0, (list, tuple)) or len(x0) != B or _ragged_geometry(x0, 1, "z") != (frames, F_):
+                raise ValueError("the start state of a ragged batch is a list with the shapes of y's utterances")
+            x0 = torch.cat([check_tensor(x, "z", torch.complex64, self.device).reshape(-1) for x in x0])
+        out, nfe = self._ode_call(self.lib.sgmse_ode_sample_each, Y, B, F_, T, frames, B, values, None, x0, seed, streams, affine_fn)
+        outs, o = [], 0                         # unpack: one [1,F,T_b] tensor per utterance
+        for T_b in frames:
+            outs.append(out[o:o + F_ * T_b].reshape(1, F_, T_b))
+            o += F_ * T_b
+        return outs, nfe
 
     def ode_stats_each(self):
         """The last ``ode_sample(step_control="utterance")`` run: dict(utterances=[dict(nfe=..., accepted=..., rejected=...,
@@ -554,7 +533,8 @@ class Context:
         return dict(utterances=utts, rounds=rounds.value, wasted=wasted.value)
 
     def ode_stats(self):
-        """The last ``ode_sample`` run: dict(accepted=..., rejected=..., t=[accepted time points])."""
+        """The last ``ode_sample`` run: dict(accepted=..., rejected=..., t=[accepted time points]) (of utterance 0 after a
+        ``step_control="utterance"`` run)."""
         acc, rej = _I(0), _I(0)
         self.check(self.lib.sgmse_ode_stats(self.h, C.byref(acc), C.byref(rej), None, 0))
         ts = (C.c_double * max(acc.value, 1))()

@@ -26,6 +26,28 @@ int sg_guard(sgmse_ctx* ctx, Fn&& fn) {
   }
 }
 #define SG_ARG(ctx, cond, msg) do { if (!(cond)) { if (ctx) (ctx)->err = std::string("invalid argument: ") + msg; return SGMSE_EINVAL; } } while (0)
+
+// sgmse_ode_sample / sgmse_ode_sample_each: the argument checks, sgmse_ode_cfg -> OdeCfg, the run; *nfe also after a failed run
+static sgmse::OdeCfg sg_ode_cfg(const sgmse_ode_cfg* cfg) {
+  sgmse::OdeCfg o;
+  o.theta = cfg->theta; o.sigma_min = cfg->sigma_min; o.sigma_max = cfg->sigma_max; o.std1 = cfg->std1;
+  o.t_end = cfg->t_end; o.eps = cfg->eps; o.rtol = cfg->rtol; o.atol = cfg->atol; o.first_step = cfg->first_step;
+  o.max_step = cfg->max_step; o.max_nfe = cfg->max_nfe; o.coef_fn = cfg->coef_fn; o.coef_user = cfg->coef_user;
+  return o;
+}
+static int sg_ode_run(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int T, const sgmse_ode_cfg* cfg, const void* noise,
+                      const void* x0, unsigned long long seed, int* nfe, bool per_utterance) {
+  SG_ARG(ctx, Y && out && cfg && B > 0 && F > 0 && T > 0, "null pointer or non-positive shape");
+  SG_ARG(ctx, cfg->rtol > 0 && cfg->atol >= 0, "rtol must be positive and atol non-negative");
+  SG_ARG(ctx, cfg->first_step >= 0 && cfg->max_step >= 0, "first_step and max_step must not be negative (0: automatic / no limit)");
+  SG_ARG(ctx, cfg->max_nfe >= 1, "max_nfe must be >= 1");
+  SG_ARG(ctx, !(noise && x0), "give replayed noise or a start state, not both");
+  return sg_guard(ctx, [&](sgmse::Engine& e) {
+    try { e.ode_run((const float2*)Y, (float2*)out, B, F, T, sg_ode_cfg(cfg), (const float2*)noise, (const float2*)x0, seed, per_utterance); }
+    catch (...) { if (nfe) *nfe = e.last_nfe(); throw; }
+    if (nfe) *nfe = e.last_nfe();
+  });
+}
 }  // namespace
 
 extern "C" {
@@ -125,20 +147,7 @@ int sgmse_sb_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int 
 
 int sgmse_ode_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int T, const sgmse_ode_cfg* cfg, const void* noise,
                      const void* x0, unsigned long long seed, int* nfe) {
-  SG_ARG(ctx, Y && out && cfg && B > 0 && F > 0 && T > 0, "null pointer or non-positive shape");
-  SG_ARG(ctx, cfg->rtol > 0 && cfg->atol >= 0, "rtol must be positive and atol non-negative");
-  SG_ARG(ctx, cfg->first_step >= 0 && cfg->max_step >= 0, "first_step and max_step must not be negative (0: automatic / no limit)");
-  SG_ARG(ctx, cfg->max_nfe >= 1, "max_nfe must be >= 1");
-  SG_ARG(ctx, !(noise && x0), "give replayed noise or a start state, not both");
-  return sg_guard(ctx, [&](sgmse::Engine& e) {
-    sgmse::OdeCfg o;
-    o.theta = cfg->theta; o.sigma_min = cfg->sigma_min; o.sigma_max = cfg->sigma_max; o.std1 = cfg->std1;
-    o.t_end = cfg->t_end; o.eps = cfg->eps; o.rtol = cfg->rtol; o.atol = cfg->atol; o.first_step = cfg->first_step;
-    o.max_step = cfg->max_step; o.max_nfe = cfg->max_nfe; o.coef_fn = cfg->coef_fn; o.coef_user = cfg->coef_user;
-    try { e.ode_sample((const float2*)Y, (float2*)out, B, F, T, o, (const float2*)noise, (const float2*)x0, seed); }
-    catch (...) { if (nfe) *nfe = e.last_nfe(); throw; }
-    if (nfe) *nfe = e.last_nfe();
-  });
+  return sg_ode_run(ctx, Y, out, B, F, T, cfg, noise, x0, seed, nfe, false);
 }
 
 int sgmse_ode_stats(sgmse_ctx* ctx, int* accepted, int* rejected, double* t_accepted, int cap) {
@@ -148,20 +157,7 @@ int sgmse_ode_stats(sgmse_ctx* ctx, int* accepted, int* rejected, double* t_acce
 
 int sgmse_ode_sample_each(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int T, const sgmse_ode_cfg* cfg, const void* noise,
                           const void* x0, unsigned long long seed, int* nfe_max) {
-  SG_ARG(ctx, Y && out && cfg && B > 0 && F > 0 && T > 0, "null pointer or non-positive shape");
-  SG_ARG(ctx, cfg->rtol > 0 && cfg->atol >= 0, "rtol must be positive and atol non-negative");
-  SG_ARG(ctx, cfg->first_step >= 0 && cfg->max_step >= 0, "first_step and max_step must not be negative (0: automatic / no limit)");
-  SG_ARG(ctx, cfg->max_nfe >= 1, "max_nfe must be >= 1");
-  SG_ARG(ctx, !(noise && x0), "give replayed noise or a start state, not both");
-  return sg_guard(ctx, [&](sgmse::Engine& e) {
-    sgmse::OdeCfg o;
-    o.theta = cfg->theta; o.sigma_min = cfg->sigma_min; o.sigma_max = cfg->sigma_max; o.std1 = cfg->std1;
-    o.t_end = cfg->t_end; o.eps = cfg->eps; o.rtol = cfg->rtol; o.atol = cfg->atol; o.first_step = cfg->first_step;
-    o.max_step = cfg->max_step; o.max_nfe = cfg->max_nfe; o.coef_fn = cfg->coef_fn; o.coef_user = cfg->coef_user;
-    try { e.ode_sample_each((const float2*)Y, (float2*)out, B, F, T, o, (const float2*)noise, (const float2*)x0, seed); }
-    catch (...) { if (nfe_max) *nfe_max = e.last_nfe(); throw; }
-    if (nfe_max) *nfe_max = e.last_nfe();
-  });
+  return sg_ode_run(ctx, Y, out, B, F, T, cfg, noise, x0, seed, nfe_max, true);
 }
 
 int sgmse_ode_stats_each(sgmse_ctx* ctx, int b, int* nfe, int* accepted, int* rejected, double* t_accepted, int cap, int* rounds,

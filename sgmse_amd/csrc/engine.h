@@ -20,7 +20,6 @@
 #include "kernels_norm_fir.h"
 #include "kernels_attn_misc.h"
 #include "kernels_ode.h"
-#include "kernels_ode_each.h"
 #include "ode_control.h"
 #include "kernels_stft.h"
 
@@ -320,7 +319,7 @@ struct SamplerCfg {
   int use_graph = 1;
 };
 
-// Engine::ode_sample (adaptive probability-flow sampler, kernels_ode.h)
+// Engine::ode_run (adaptive probability-flow sampler, kernels_ode.h)
 struct OdeCfg {
   float theta = 1.5f, sigma_min = 0.05f, sigma_max = 0.5f;
   float std1 = 0.f;                       // OUVE._std(T) for the prior draw
@@ -347,7 +346,6 @@ class Engine {
     if (graph_valid_ || graph_stale_) drt::graph_destroy(&graph_);
     if (hstage_) drt::free_host(hstage_);
     if (ode_host_) drt::free_host(ode_host_);
-    if (ode_ehost_) drt::free_host(ode_ehost_);
     if (hstage_ev_init_) drt::event_destroy(&hstage_ev_);
     for (drt::event_t& e : side_ev_) drt::event_destroy(&e);
     if (side_stream_ready_) drt::stream_destroy(side_stream_);
@@ -574,23 +572,36 @@ class Engine {
     return (double)(g * g * 0.5f);
   }
   // get_ode_sampler(..., denoise=False)() (sampling/__init__.py:96-143) with the solver inside the library: scipy's RK45
-  // (Dormand-Prince 5(4), scipy/integrate/_ivp/rk.py) and its step control (common.py select_initial_step, RungeKutta._step_impl)
-  // over the flattened batch -- ONE error norm for all B*F*T complex elements, as scipy sees the state, so the utterances of a batch
-  // are coupled exactly as in the reference.  State, slopes and error estimate stay on the device (kernels_ode.h); the host runs the
-  // step control in double and reads one scalar, the error norm, per attempted step.  The evaluation count is scipy's nfev.
+  // (Dormand-Prince 5(4), scipy/integrate/_ivp/rk.py) and its step control (common.py select_initial_step, RungeKutta._step_impl),
+  // one controller (ode_control.h) per GROUP of the batch (kernels_ode.h).  State, slopes and error estimates stay on the device; the
+  // host runs the step control in double and reads one scalar, the error norm, per group and attempted step.
+  //   batch control (sgmse_ode_sample): G = 1, the flattened rectangular batch -- ONE error norm for all B*F*T complex elements, as
+  //     scipy sees the state, so the utterances of a batch are coupled exactly as in the reference; the evaluation count is scipy's nfev.
+  //   per-utterance control (sgmse_ode_sample_each): G = B, group g = utterance g of a uniform or ragged (sgmse_set_frames: packed
+  //     tensors, as pc_sample takes them) batch, each with its own initial step, stage times, error norm, accept / reject decisions
+  //     and end of integration, all fed by ONE batch evaluation per stage.  Utterance b's result, evaluation count, step counts and
+  //     accepted times are those of batch control on that utterance alone: it is the same code with another number of groups.  A
+  //     finished utterance is frozen: the network still evaluates its slot (at its last stage input, at t = eps), nothing of it is
+  //     written.  max_nfe caps every utterance's own count; last_nfe() is the number of batch evaluations (the largest utterance's).
+  // A "round" is one attempted step of every unfinished group: six batch evaluations at 6 G time-embedding rows (row = stage * G +
+  // group), one table of [G][ODE_ROWS][ODE_STRIDE] doubles up, G error sums back.  coef_fn is called once per upload with its nt G
+  // times STAGE-MAJOR (t[stage * G + g]): nt = 1 for f0 and for the probe of select_initial_step, 6 for a round.
   // Prior: x0 (given start state), else y + std1 z with z = noise (replayed, [B][F][T]) or the Philox stream of (seed, streams).
-  void ode_sample(const float2* Y, float2* out, int B, int F, int T, const OdeCfg& oc, const float2* noise, const float2* x0,
-                  unsigned long long seed) {
+  void ode_run(const float2* Y, float2* out, int B, int F, int T, const OdeCfg& oc, const float2* noise, const float2* x0,
+               unsigned long long seed, bool per_utterance) {
     require_ready();
-    SG_REQUIRE(!ragged(), "ode_sample: ragged batches are not supported: the solver's error norm couples the utterances of a batch "
-                          "(call sgmse_set_frames with n = 0 and pass a rectangular batch)");
-    // (rtol, atol, first_step, max_step, max_nfe: checked once, at the C boundary, sgmse_ode_sample)
-    SG_REQUIRE(oc.t_end != oc.eps && oc.eps > 0 && oc.t_end > 0, "ode_sample: bad time span");
-    SG_REQUIRE(oc.sigma_min > 0 && oc.sigma_max > oc.sigma_min, "ode_sample: bad sigma range");
-    const double interval = std::fabs(oc.eps - oc.t_end), dir = oc.eps < oc.t_end ? -1.0 : 1.0;
-    SG_REQUIRE(oc.first_step <= interval, "ode_sample: `first_step` exceeds bounds");
-    ensure_shape(B, F, T, ODE_ROWS);
-    const size_t n = (size_t)B * F * T;
+    const std::string who = per_utterance ? "ode_sample_each" : "ode_sample";
+    SG_REQUIRE(per_utterance || !ragged(), "ode_sample: ragged batches are not supported: the solver's error norm couples the utterances of a batch "
+                                           "(call sgmse_set_frames with n = 0 and pass a rectangular batch)");
+    // (rtol, atol, first_step, max_step, max_nfe: checked once, at the C boundary)
+    SG_REQUIRE(oc.t_end != oc.eps && oc.eps > 0 && oc.t_end > 0, who + ": bad time span");
+    SG_REQUIRE(oc.sigma_min > 0 && oc.sigma_max > oc.sigma_min, who + ": bad sigma range");
+    SG_REQUIRE(oc.first_step <= std::fabs(oc.eps - oc.t_end), who + ": `first_step` exceeds bounds");
+    SG_REQUIRE(!per_utterance || B <= kOdeEachMaxB, "ode_sample_each: batch too large");
+    const int G = per_utterance ? B : 1;
+    ensure_shape(B, F, T, ODE_ROWS * G);
+    const size_t n = ragged() ? rag_pix_[0] : (size_t)B * F * T;     // complex elements, utterance after utterance
+    const size_t per = per_utterance ? (size_t)F * T : n;            // ... of a group (ragged: of the longest)
     if (n > ode_n_) {
       for (float2** q : {&ode_k_[0], &ode_k_[1], &ode_k_[2], &ode_k_[3], &ode_k_[4], &ode_k_[5], &ode_k_[6], &ode_xs_}) {
         if (*q) dev_free_owned(*q);
@@ -598,13 +609,25 @@ class Engine {
       }
       ode_n_ = n;
     }
-    if (!ode_table_) {
-      ode_table_ = static_cast<double*>(dev_alloc(sizeof(double) * ODE_ROWS * ODE_STRIDE));
-      ode_partial_ = static_cast<double*>(dev_alloc(sizeof(double) * ODE_NBLK * ODE_NSUM));
-      ode_result_ = static_cast<double*>(dev_alloc(sizeof(double) * ODE_NSUM));
-      SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&ode_host_), sizeof(double) * ODE_NSUM));
+    if (G > ode_cap_) {
+      for (double** q : {&ode_table_, &ode_partial_, &ode_result_}) if (*q) dev_free_owned(*q);
+      if (ode_host_) drt::free_host(ode_host_);
+      ode_table_ = static_cast<double*>(dev_alloc(sizeof(double) * G * ODE_ROWS * ODE_STRIDE));
+      ode_partial_ = static_cast<double*>(dev_alloc(sizeof(double) * G * ODE_NBLK * ODE_NSUM));
+      ode_result_ = static_cast<double*>(dev_alloc(sizeof(double) * G * ODE_NSUM));
+      ode_host_ = nullptr;
+      SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&ode_host_), sizeof(double) * G * ODE_NSUM));
+      ode_cap_ = G;
     }
-    ode_accepted_ = ode_rejected_ = 0; ode_t_acc_.clear(); nfe_ = 0;
+    ode_ctl_.assign(G, OdeControl());
+    ode_rounds_ = ode_wasted_ = 0; nfe_ = 0;
+    std::vector<OdeControl>& cs = ode_ctl_;
+    std::vector<size_t> goff(G), glen(G);                            // the groups' ranges, in complex elements
+    for (int g = 0; g < G; ++g) {
+      goff[g] = ragged() ? (size_t)F * rag_prefix(g) : (size_t)g * per;
+      glen[g] = ragged() ? (size_t)F * rag_T_[g] : per;
+      cs[g].start(oc.t_end, oc.eps, oc.max_step, (double)glen[g]);
+    }
 
     // prior
     const std::vector<float> one_row(SC_STRIDE, 0.f), one_t(1, (float)oc.t_end);
@@ -615,218 +638,45 @@ class Engine {
     } else {
       SamplerArgs sa{};
       sa.x = sx_; sa.y = sy_; sa.noise = noise; sa.seed = seed_dev; sa.std1 = oc.std1; sa.n = (int)n; sa.B = B; sa.per = F * T;
-      DRT_LAUNCH(sampler_prior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), stream_, sa);
-    }
-
-    float2 *xcur = sx_, *xnew = sxm_;
-    float2* K[7];
-    for (int j = 0; j < 7; ++j) K[j] = ode_k_[j];
-    FwdCtl ctl{bias_table_, 0, tot_temb_, step_ctr_, tsteps_, 0, 1, -1.0f};
-    if (oc.coef_fn) { ctl.coef = coef_table_; ctl.coef_bstride = 0; ctl.coef_sstride = 1; }
-    const long long FT = (long long)F * T;
-    const unsigned egrid = (unsigned)std::min<size_t>((n / 2 + 255) / 256 + 1, 4096);
-    auto base_args = [&]() {
-      OdeArgs a{};
-      a.x = (const float*)xcur; a.y = (const float*)sy_; a.score = (const float*)sscore_;
-      for (int j = 0; j < 7; ++j) a.k[j] = (const float*)K[j];
-      a.table = ode_table_; a.step_ptr = step_ctr_; a.row = -1; a.theta = oc.theta; a.nfl = (long long)(2 * n);
-      a.atol = oc.atol; a.rtol = oc.rtol; a.partial = ode_partial_; a.result = ode_result_;
-      return a;
-    };
-    // stage times + scalar table (+ score-wrapper rows) of one attempt -> device through the pinned staging buffer; time embedding
-    // rows 0..nt-1; step counter to row 0
-    auto upload = [&](const double* times, int nt, double* table) {
-      float tf[ODE_ROWS] = {0}, cf[ODE_ROWS * 4] = {0};
-      for (int e = 0; e < nt; ++e) { tf[e] = (float)times[e]; table[e * ODE_STRIDE] = ode_g2half(oc, tf[e]); }
-      if (oc.coef_fn) {
-        float ga[ODE_ROWS], al[ODE_ROWS], be[ODE_ROWS];
-        oc.coef_fn(oc.coef_user, nt, tf, ga, al, be);
-        for (int e = 0; e < nt; ++e) {
-          SG_REQUIRE(std::isfinite(ga[e]) && std::isfinite(al[e]) && std::isfinite(be[e]), "ode_sample: the score-wrapper callback returned a non-finite coefficient");
-          cf[4 * e] = ga[e]; cf[4 * e + 1] = al[e]; cf[4 * e + 2] = be[e];
-        }
-      }
-      if (hstage_pending_) { SG_CHECK(drt::event_sync(&hstage_ev_)); hstage_pending_ = false; }
-      const size_t nb_t = sizeof tf, nb_c = sizeof cf, nb_tab = sizeof(double) * ODE_ROWS * ODE_STRIDE;
-      SG_REQUIRE(hstage_ && hstage_cap_ >= nb_t + nb_c + nb_tab, "ode_sample: staging buffer missing");
-      memcpy(hstage_, table, nb_tab); memcpy(hstage_ + nb_tab, tf, nb_t); memcpy(hstage_ + nb_tab + nb_t, cf, nb_c);
-      SG_CHECK(drt::memcpy_h2d(ode_table_, hstage_, nb_tab, stream_));
-      SG_CHECK(drt::memcpy_h2d(tsteps_, hstage_ + nb_tab, nb_t, stream_));
-      if (oc.coef_fn) SG_CHECK(drt::memcpy_h2d(coef_table_, hstage_ + nb_tab + nb_t, nb_c, stream_));
-      SG_CHECK(drt::event_record(&hstage_ev_, stream_));
-      hstage_pending_ = true;
-      compute_temb(tsteps_, nt);
-      DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_, 0);
-    };
-    auto evaluate = [&](const float2* at) {      // one network evaluation at the step counter's time row
-      arena_.reset();
-      run_forward(at, FT, sy_, FT, sscore_, B, F, T, ctl);
-    };
-    auto read_sums = [&](double* s) {            // second stage of a reduction + the one scalar transfer of an attempt
-      DRT_LAUNCH(ode_reduce_final_kernel, dim3(1), dim3(64), stream_, (const double*)ode_partial_, ode_result_);
-      SG_CHECK(drt::memcpy_d2h(ode_host_, ode_result_, sizeof(double) * ODE_NSUM, stream_));
-      SG_CHECK(drt::stream_sync(stream_));
-      check_launch();
-      s[0] = ode_host_[0]; s[1] = ode_host_[1];
-    };
-    auto count = [&](int k) {
-      SG_REQUIRE(nfe_ + k <= oc.max_nfe, "ode_sample: the solver needs more than max_nfe = " + std::to_string(oc.max_nfe) + " evaluations (t = " +
-                 std::to_string(ode_t_acc_.empty() ? oc.t_end : ode_t_acc_.back()) + ")");
-      nfe_ += k;
-    };
-
-    OdeControl c;                  // the step control (ode_control.h): one controller for the whole flattened batch
-    c.start(oc.t_end, oc.eps, oc.max_step, (double)n);
-    double table[ODE_ROWS * ODE_STRIDE];
-    // f0 = f(t0, y0)
-    count(1);
-    memset(table, 0, sizeof table);
-    upload(&c.t, 1, table);
-    evaluate(xcur);
-    { OdeArgs a = base_args(); a.xs = a.x; a.kout = (float*)K[0]; a.self = 0; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
-
-    if (oc.first_step > 0) {
-      c.h_abs = oc.first_step;
-    } else {      // select_initial_step
-      count(1);
-      double s[2];
-      { OdeArgs a = base_args(); a.k[1] = nullptr; DRT_LAUNCH(ode_init_norms_kernel, dim3(ODE_NBLK), dim3(256), stream_, a); }
-      read_sums(s);
-      const double h0 = c.probe_step(s[0], s[1]);
-      memset(table, 0, sizeof table);
-      table[6 * ODE_STRIDE + 1] = h0 * c.dir;
-      const double t1 = c.t + h0 * c.dir;
-      upload(&t1, 1, table);
-      { OdeArgs a = base_args(); a.row = 6; a.nterms = 1; a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
-      evaluate(ode_xs_);
-      { OdeArgs a = base_args(); a.xs = (const float*)ode_xs_; a.kout = (float*)K[6]; a.self = 6; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
-      { OdeArgs a = base_args(); a.k[0] = (const float*)K[6]; a.k[1] = (const float*)K[0]; DRT_LAUNCH(ode_init_norms_kernel, dim3(ODE_NBLK), dim3(256), stream_, a); }
-      read_sums(s);
-      c.first_step_from_probe(s[1]);
-    }
-
-    while (!c.done()) {
-      SG_REQUIRE(c.begin_attempt(), "ode_sample: required step size is less than spacing between numbers (t = " + std::to_string(c.t) + ")");
-      count(6);
-      // ---- one attempted step: six evaluations, one scalar back
-      double times[6];
-      memset(table, 0, sizeof table);
-      c.fill_attempt(times, table, ODE_STRIDE);
-      upload(times, 6, table);
-      { OdeArgs a = base_args(); a.row = 6; a.nterms = 1; a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a); }
-      for (int e = 0; e < 5; ++e) {
-        evaluate(ode_xs_);
-        OdeArgs a = base_args();
-        a.xs = (const float*)ode_xs_; a.kout = (float*)K[e + 1]; a.self = e + 1; a.nterms = e + 2;
-        a.xnext = e < 4 ? (float*)ode_xs_ : (float*)xnew;
-        DRT_LAUNCH(ode_stage_kernel, dim3(egrid), dim3(256), stream_, a);
-        DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
-      }
-      evaluate(xnew);
-      { OdeArgs a = base_args(); a.xnew = (const float*)xnew; a.kout = (float*)K[6]; DRT_LAUNCH(ode_error_kernel, dim3(ODE_NBLK), dim3(256), stream_, a); }
-      double s[2];
-      read_sums(s);
-      if (c.finish_attempt(s[0])) {
-        std::swap(xcur, xnew);
-        std::swap(K[0], K[6]);       // first same as last
-        ++ode_accepted_;
-        ode_t_acc_.push_back(c.t);
-      } else {
-        ++ode_rejected_;
-      }
-    }
-    SG_CHECK(drt::memcpy_d2d(out, xcur, n * 8, stream_));
-  }
-  // The same solver with PER-UTTERANCE step control (kernels_ode_each.h): B controllers, one per utterance of a uniform or ragged
-  // (sgmse_set_frames: packed tensors, as pc_sample takes them) batch, each with its own initial step, stage times, error norm,
-  // accept / reject decisions and end of integration, all fed by ONE batch evaluation per stage.  A "round" is one attempted step of
-  // every unfinished utterance: six batch evaluations at 6 B time-embedding rows (row = stage * B + utterance), one table of
-  // [B][ODE_ROWS][ODE_STRIDE] doubles up, B error sums back.  Utterance b's result, evaluation count, step counts and accepted times
-  // are those of ode_sample on that utterance alone (B = 1): same controller code, same kernels bodies, same summation order.  A
-  // finished utterance is frozen: the network still evaluates its slot (at its last stage input, at t = eps), nothing of it is written.
-  // coef_fn is called once per round with the 6 B stage times STAGE-MAJOR (t[stage * B + b]); max_nfe caps every utterance's own count.
-  void ode_sample_each(const float2* Y, float2* out, int B, int F, int T, const OdeCfg& oc, const float2* noise, const float2* x0,
-                       unsigned long long seed) {
-    require_ready();
-    SG_REQUIRE(oc.t_end != oc.eps && oc.eps > 0 && oc.t_end > 0, "ode_sample_each: bad time span");
-    SG_REQUIRE(oc.sigma_min > 0 && oc.sigma_max > oc.sigma_min, "ode_sample_each: bad sigma range");
-    const double interval = std::fabs(oc.eps - oc.t_end);
-    SG_REQUIRE(oc.first_step <= interval, "ode_sample_each: `first_step` exceeds bounds");
-    SG_REQUIRE(B <= kOdeEachMaxB, "ode_sample_each: batch too large");
-    ensure_shape(B, F, T, ODE_ROWS * B);
-    const size_t n = ragged() ? rag_pix_[0] : (size_t)B * F * T;     // complex elements, utterance after utterance
-    if (n > ode_n_) {
-      for (float2** q : {&ode_k_[0], &ode_k_[1], &ode_k_[2], &ode_k_[3], &ode_k_[4], &ode_k_[5], &ode_k_[6], &ode_xs_}) {
-        if (*q) dev_free_owned(*q);
-        *q = static_cast<float2*>(dev_alloc(n * 8));
-      }
-      ode_n_ = n;
-    }
-    if (B > ode_each_cap_) {
-      for (double** q : {&ode_etable_, &ode_epartial_, &ode_eresult_}) if (*q) dev_free_owned(*q);
-      if (ode_ehost_) drt::free_host(ode_ehost_);
-      ode_etable_ = static_cast<double*>(dev_alloc(sizeof(double) * B * ODE_ROWS * ODE_STRIDE));
-      ode_epartial_ = static_cast<double*>(dev_alloc(sizeof(double) * B * ODE_NBLK * ODE_NSUM));
-      ode_eresult_ = static_cast<double*>(dev_alloc(sizeof(double) * B * ODE_NSUM));
-      ode_ehost_ = nullptr;
-      SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&ode_ehost_), sizeof(double) * B * ODE_NSUM));
-      ode_each_cap_ = B;
-    }
-    ode_each_.assign(B, OdeControl());
-    ode_rounds_ = ode_wasted_ = 0; nfe_ = 0;
-    std::vector<OdeControl>& cs = ode_each_;
-    std::vector<double> npix(B);
-    for (int b = 0; b < B; ++b) {
-      npix[b] = ragged() ? (double)F * rag_T_[b] : (double)F * T;
-      cs[b].start(oc.t_end, oc.eps, oc.max_step, npix[b]);
-    }
-
-    // prior
-    const std::vector<float> one_row(SC_STRIDE, 0.f), one_t(1, (float)oc.t_end);
-    const unsigned long long* seed_dev = upload_tables(one_row, one_t, std::vector<float>(), seed, B);
-    SG_CHECK(drt::memcpy_d2d(sy_, Y, n * 8, stream_));
-    if (x0) {
-      SG_CHECK(drt::memcpy_d2d(sx_, x0, n * 8, stream_));
-    } else {
-      SamplerArgs sa{};
-      sa.x = sx_; sa.y = sy_; sa.noise = noise; sa.seed = seed_dev; sa.std1 = oc.std1; sa.n = (int)n; sa.B = B; sa.per = F * T;
       sa.rag_off = ragged() ? rag_off_dev_[0] : nullptr;
       DRT_LAUNCH(sampler_prior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), stream_, sa);
     }
 
-    // time-embedding / time / wrapper rows: row = stage * B + utterance
-    FwdCtl ctl{bias_table_, tot_temb_, B * tot_temb_, step_ctr_, tsteps_, 1, B, -1.0f};
-    if (oc.coef_fn) { ctl.coef = coef_table_; ctl.coef_bstride = 1; ctl.coef_sstride = B; }
+    // time-embedding / time / wrapper rows: row = stage * G + group; the network's batch stride over them is 1 row when every
+    // utterance is a group and 0 when the batch is one
+    const int bs = per_utterance ? 1 : 0;
+    FwdCtl ctl{bias_table_, bs * tot_temb_, G * tot_temb_, step_ctr_, tsteps_, bs, G, -1.0f};
+    if (oc.coef_fn) { ctl.coef = coef_table_; ctl.coef_bstride = bs; ctl.coef_sstride = G; }
     const long long FT = ragged() ? 1 : (long long)F * T;            // batch stride of x / y (ragged: multiplier of the utterance's offset)
-    const unsigned egrid = (unsigned)std::min<size_t>(((size_t)F * T / 2 + 255) / 256 + 1, 4096);      // per utterance
-    std::vector<int> sel(B, 0);                                        // host copy of the selectors (kernels_ode_each.h)
+    const unsigned egrid = (unsigned)std::min<size_t>((per / 2 + 255) / 256 + 1, 4096);      // per group
+    std::vector<int> sel(G, 0);                                        // host copy of the selectors (kernels_ode.h)
     auto base_args = [&]() {
       OdeEachArgs e{};
       OdeArgs& a = e.a;
       a.y = (const float*)sy_; a.score = (const float*)sscore_;
       for (int j = 1; j < 6; ++j) a.k[j] = (const float*)ode_k_[j];
-      a.table = ode_etable_; a.step_ptr = step_ctr_; a.row = -1; a.theta = oc.theta;
-      a.atol = oc.atol; a.rtol = oc.rtol; a.partial = ode_epartial_; a.result = ode_eresult_;
+      a.table = ode_table_; a.step_ptr = step_ctr_; a.row = -1; a.theta = oc.theta;
+      a.atol = oc.atol; a.rtol = oc.rtol; a.partial = ode_partial_; a.result = ode_result_;
       e.xbuf[0] = (float*)sx_; e.xbuf[1] = (float*)sxm_; e.kbuf[0] = (float*)ode_k_[0]; e.kbuf[1] = (float*)ode_k_[6];
-      e.rag_off = ragged() ? rag_off_dev_[0] : nullptr; e.per = (long long)F * T; e.kout_sel = -1;
+      e.rag_off = ragged() ? rag_off_dev_[0] : nullptr; e.per = (long long)per; e.kout_sel = -1;
       return e;
     };
-    const size_t tab_doubles = (size_t)B * ODE_ROWS * ODE_STRIDE;
-    std::vector<double> table(tab_doubles), times((size_t)ODE_ROWS * B);
-    std::vector<float> tf((size_t)ODE_ROWS * B), cf((size_t)ODE_ROWS * B * 4), ga((size_t)ODE_ROWS * B), al(ga.size()), be(ga.size());
-    // one round's table (rows 0..6 of the active utterances filled by the caller; row 7 = selector, active flag), nt * B stage times
-    // (times[e * B + b]) and wrapper rows -> device through the pinned staging buffer; time embedding rows; step counter to row 0
+    const size_t tab_doubles = (size_t)G * ODE_ROWS * ODE_STRIDE;
+    std::vector<double> table(tab_doubles), times((size_t)ODE_ROWS * G);
+    std::vector<float> tf((size_t)ODE_ROWS * G), cf((size_t)ODE_ROWS * G * 4), ga((size_t)ODE_ROWS * G), al(ga.size()), be(ga.size());
+    // one round's table (rows 0..6 of the active groups filled by the caller; row 7 = selector, active flag), nt * G stage times
+    // (times[e * G + g]) and wrapper rows -> device through the pinned staging buffer; time embedding rows; step counter to row 0
     auto upload = [&](int nt, const std::vector<char>& active) {
-      const int rows = nt * B;
-      for (int b = 0; b < B; ++b) {
-        double* tb = &table[(size_t)b * ODE_ROWS * ODE_STRIDE];
-        for (int e = 0; e < nt; ++e) { tf[(size_t)e * B + b] = (float)times[(size_t)e * B + b]; tb[e * ODE_STRIDE] = ode_g2half(oc, tf[(size_t)e * B + b]); }
-        tb[ODE_ROW_STATE * ODE_STRIDE] = (double)sel[b]; tb[ODE_ROW_STATE * ODE_STRIDE + 1] = active[b] ? 1.0 : 0.0;
+      const int rows = nt * G;
+      for (int g = 0; g < G; ++g) {
+        double* tb = &table[(size_t)g * ODE_ROWS * ODE_STRIDE];
+        for (int e = 0; e < nt; ++e) { tf[(size_t)e * G + g] = (float)times[(size_t)e * G + g]; tb[e * ODE_STRIDE] = ode_g2half(oc, tf[(size_t)e * G + g]); }
+        tb[ODE_ROW_STATE * ODE_STRIDE] = (double)sel[g]; tb[ODE_ROW_STATE * ODE_STRIDE + 1] = active[g] ? 1.0 : 0.0;
       }
       if (oc.coef_fn) {
         oc.coef_fn(oc.coef_user, rows, tf.data(), ga.data(), al.data(), be.data());
         for (int r = 0; r < rows; ++r) {
-          SG_REQUIRE(std::isfinite(ga[r]) && std::isfinite(al[r]) && std::isfinite(be[r]), "ode_sample_each: the score-wrapper callback returned a non-finite coefficient");
+          SG_REQUIRE(std::isfinite(ga[r]) && std::isfinite(al[r]) && std::isfinite(be[r]), who + ": the score-wrapper callback returned a non-finite coefficient");
           cf[4 * (size_t)r] = ga[r]; cf[4 * (size_t)r + 1] = al[r]; cf[4 * (size_t)r + 2] = be[r]; cf[4 * (size_t)r + 3] = 0.f;
         }
       }
@@ -839,7 +689,7 @@ class Engine {
         hstage_cap_ = nb_tab + nb_t + nb_c;
       }
       memcpy(hstage_, table.data(), nb_tab); memcpy(hstage_ + nb_tab, tf.data(), nb_t); memcpy(hstage_ + nb_tab + nb_t, cf.data(), nb_c);
-      SG_CHECK(drt::memcpy_h2d(ode_etable_, hstage_, nb_tab, stream_));
+      SG_CHECK(drt::memcpy_h2d(ode_table_, hstage_, nb_tab, stream_));
       SG_CHECK(drt::memcpy_h2d(tsteps_, hstage_ + nb_tab, nb_t, stream_));
       if (oc.coef_fn) SG_CHECK(drt::memcpy_h2d(coef_table_, hstage_ + nb_tab + nb_t, nb_c, stream_));
       SG_CHECK(drt::event_record(&hstage_ev_, stream_));
@@ -852,39 +702,40 @@ class Engine {
       run_forward(at, FT, sy_, FT, sscore_, B, F, T, ctl);
       ++nfe_;
     };
-    auto read_sums = [&]() {                     // second stage of a reduction + the one transfer of a round: B x ODE_NSUM doubles
-      DRT_LAUNCH(ode_reduce_final_each_kernel, dim3(B), dim3(64), stream_, (const double*)ode_etable_, (const double*)ode_epartial_, ode_eresult_);
-      SG_CHECK(drt::memcpy_d2h(ode_ehost_, ode_eresult_, sizeof(double) * B * ODE_NSUM, stream_));
+    auto read_sums = [&]() {                     // second stage of a reduction + the one transfer of a round: G x ODE_NSUM doubles
+      DRT_LAUNCH(ode_reduce_final_each_kernel, dim3(G), dim3(64), stream_, (const double*)ode_table_, (const double*)ode_partial_, ode_result_);
+      SG_CHECK(drt::memcpy_d2h(ode_host_, ode_result_, sizeof(double) * G * ODE_NSUM, stream_));
       SG_CHECK(drt::stream_sync(stream_));
       check_launch();
     };
-    auto count = [&](int b, int k) {
-      SG_REQUIRE(cs[b].nfe + k <= oc.max_nfe, "ode_sample_each: utterance " + std::to_string(b) + " needs more than max_nfe = " + std::to_string(oc.max_nfe) +
-                 " evaluations (t = " + std::to_string(cs[b].last_time(oc.t_end)) + ")");
-      cs[b].nfe += k;
+    const auto subject = [&](int g) { return who + (per_utterance ? ": utterance " + std::to_string(g) : std::string(": the solver")); };
+    auto count = [&](int g, int k) {             // checked before the evaluations run
+      SG_REQUIRE(cs[g].nfe + k <= oc.max_nfe, subject(g) + " needs more than max_nfe = " + std::to_string(oc.max_nfe) + " evaluations (t = " +
+                 std::to_string(cs[g].last_time(oc.t_end)) + ")");
+      cs[g].nfe += k;
     };
-    const dim3 sgrid(egrid, B), rgrid(ODE_NBLK, B);
-    std::vector<char> active(B, 1);
+    const dim3 sgrid(egrid, G), rgrid(ODE_NBLK, G);
+    std::vector<char> active(G, 1);
 
     // f0 = f(t0, y0): every selector is 0, the state of the whole batch is sx_
-    for (int b = 0; b < B; ++b) count(b, 1);
+    for (int g = 0; g < G; ++g) count(g, 1);
     std::fill(table.begin(), table.end(), 0.0);
-    for (int b = 0; b < B; ++b) times[b] = oc.t_end;
+    for (int g = 0; g < G; ++g) times[g] = oc.t_end;
     upload(1, active);
     evaluate(sx_);
     { OdeEachArgs e = base_args(); e.kout_sel = 0; e.a.self = 0; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
 
     if (oc.first_step > 0) {
-      for (int b = 0; b < B; ++b) cs[b].h_abs = oc.first_step;
-    } else {      // select_initial_step, per utterance: the probe evaluation at the utterance's own t0 + h0
-      for (int b = 0; b < B; ++b) count(b, 1);
+      for (int g = 0; g < G; ++g) cs[g].h_abs = oc.first_step;
+    } else {      // select_initial_step, per group: the probe evaluation at the group's own t0 + h0
+      for (int g = 0; g < G; ++g) count(g, 1);
       { OdeEachArgs e = base_args(); e.d2 = 0; DRT_LAUNCH(ode_init_norms_each_kernel, rgrid, dim3(256), stream_, e); }
       read_sums();
       std::fill(table.begin(), table.end(), 0.0);
-      for (int b = 0; b < B; ++b) {
-        const double h0 = cs[b].probe_step(ode_ehost_[b * ODE_NSUM], ode_ehost_[b * ODE_NSUM + 1]);
-        table[((size_t)b * ODE_ROWS + 6) * ODE_STRIDE + 1] = h0 * cs[b].dir;
-        times[b] = cs[b].t + h0 * cs[b].dir;
+      for (int g = 0; g < G; ++g) {
+        const double h0 = cs[g].probe_step(ode_host_[g * ODE_NSUM], ode_host_[g * ODE_NSUM + 1]);
+        table[((size_t)g * ODE_ROWS + 6) * ODE_STRIDE + 1] = h0 * cs[g].dir;
+        times[g] = cs[g].t + h0 * cs[g].dir;
       }
       upload(1, active);
       { OdeEachArgs e = base_args(); e.a.row = 6; e.a.nterms = 1; e.a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
@@ -892,25 +743,25 @@ class Engine {
       { OdeEachArgs e = base_args(); e.a.xs = (const float*)ode_xs_; e.kout_sel = 6; e.a.self = 6; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
       { OdeEachArgs e = base_args(); e.d2 = 1; DRT_LAUNCH(ode_init_norms_each_kernel, rgrid, dim3(256), stream_, e); }
       read_sums();
-      for (int b = 0; b < B; ++b) cs[b].first_step_from_probe(ode_ehost_[b * ODE_NSUM + 1]);
+      for (int g = 0; g < G; ++g) cs[g].first_step_from_probe(ode_host_[g * ODE_NSUM + 1]);
     }
 
     for (;;) {
       int nactive = 0;
-      for (int b = 0; b < B; ++b) { active[b] = cs[b].done() ? 0 : 1; nactive += active[b]; }
+      for (int g = 0; g < G; ++g) { active[g] = cs[g].done() ? 0 : 1; nactive += active[g]; }
       if (!nactive) break;
-      // ---- one round: an attempted step of every unfinished utterance; six batch evaluations, B scalars back
+      // ---- one round: an attempted step of every unfinished group; six batch evaluations, G scalars back
       std::fill(table.begin(), table.end(), 0.0);
-      for (int b = 0; b < B; ++b) {
-        if (!active[b]) { for (int e = 0; e < 6; ++e) times[(size_t)e * B + b] = cs[b].t; continue; }      // (frozen: any valid time)
-        SG_REQUIRE(cs[b].begin_attempt(), "ode_sample_each: utterance " + std::to_string(b) + ": required step size is less than spacing between numbers (t = " +
-                   std::to_string(cs[b].t) + ")");
-        count(b, 6);
+      for (int g = 0; g < G; ++g) {
+        if (!active[g]) { for (int e = 0; e < 6; ++e) times[(size_t)e * G + g] = cs[g].t; continue; }      // (frozen: any valid time)
+        SG_REQUIRE(cs[g].begin_attempt(), (per_utterance ? subject(g) : who) + ": required step size is less than spacing between numbers (t = " +
+                   std::to_string(cs[g].t) + ")");
+        count(g, 6);
         double tm[6];
-        cs[b].fill_attempt(tm, &table[(size_t)b * ODE_ROWS * ODE_STRIDE], ODE_STRIDE);
-        for (int e = 0; e < 6; ++e) times[(size_t)e * B + b] = tm[e];
+        cs[g].fill_attempt(tm, &table[(size_t)g * ODE_ROWS * ODE_STRIDE], ODE_STRIDE);
+        for (int e = 0; e < 6; ++e) times[(size_t)e * G + g] = tm[e];
       }
-      ++ode_rounds_; ode_wasted_ += 6 * (B - nactive);
+      ++ode_rounds_; ode_wasted_ += 6 * (G - nactive);
       upload(6, active);
       { OdeEachArgs e = base_args(); e.a.row = 6; e.a.nterms = 1; e.a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
       for (int st = 0; st < 5; ++st) {
@@ -918,25 +769,22 @@ class Engine {
         OdeEachArgs e = base_args();
         e.a.xs = (const float*)ode_xs_; e.a.kout = (float*)ode_k_[st + 1]; e.a.self = st + 1; e.a.nterms = st + 2;
         e.a.xnext = (float*)ode_xs_;              // (in place: each thread reads its elements before it writes them)
-        e.to_new_state = st == 4 ? 1 : 0;         // y_new: to the stage-input buffer for the network AND to the utterance's other state buffer
+        e.to_new_state = st == 4 ? 1 : 0;         // y_new: to the stage-input buffer for the network AND to the group's other state buffer
         DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e);
         DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
       }
       evaluate(ode_xs_);
       { OdeEachArgs e = base_args(); DRT_LAUNCH(ode_error_each_kernel, rgrid, dim3(256), stream_, e); }
       read_sums();
-      for (int b = 0; b < B; ++b)
-        if (active[b] && cs[b].finish_attempt(ode_ehost_[b * ODE_NSUM])) sel[b] ^= 1;      // first same as last
+      for (int g = 0; g < G; ++g)
+        if (active[g] && cs[g].finish_attempt(ode_host_[g * ODE_NSUM])) sel[g] ^= 1;      // first same as last
     }
-    for (int b = 0; b < B; ++b) {
-      const size_t off = ragged() ? ((size_t)F * rag_prefix(b)) : (size_t)b * F * T, len = (size_t)npix[b];
-      SG_CHECK(drt::memcpy_d2d(out + off, (sel[b] ? sxm_ : sx_) + off, len * 8, stream_));
-    }
+    for (int g = 0; g < G; ++g) SG_CHECK(drt::memcpy_d2d(out + goff[g], (sel[g] ? sxm_ : sx_) + goff[g], glen[g] * 8, stream_));
   }
-  // utterance b of the last ode_sample_each run
+  // group b of the last ode_run (per-utterance control: utterance b; batch control: b = 0, the batch)
   void ode_stats_each(int b, int* nfe, int* accepted, int* rejected, double* t_accepted, int cap, int* rounds, int* wasted) const {
-    SG_REQUIRE(b >= 0 && b < (int)ode_each_.size(), "ode_stats_each: no such utterance in the last run");
-    const OdeControl& c = ode_each_[b];
+    SG_REQUIRE(b >= 0 && b < (int)ode_ctl_.size(), "ode_stats_each: no such utterance in the last run");
+    const OdeControl& c = ode_ctl_[b];
     if (nfe) *nfe = c.nfe;
     if (accepted) *accepted = c.n_accepted;
     if (rejected) *rejected = c.n_rejected;
@@ -945,10 +793,9 @@ class Engine {
     if (wasted) *wasted = ode_wasted_;
   }
   size_t rag_prefix(int b) const { size_t s = 0; for (int i = 0; i < b; ++i) s += (size_t)rag_T_[i]; return s; }      // frames before utterance b
-  void ode_stats(int* accepted, int* rejected, double* t_accepted, int cap) const {
-    if (accepted) *accepted = ode_accepted_;
-    if (rejected) *rejected = ode_rejected_;
-    for (int i = 0; t_accepted && i < cap && i < (int)ode_t_acc_.size(); ++i) t_accepted[i] = ode_t_acc_[i];
+  void ode_stats(int* accepted, int* rejected, double* t_accepted, int cap) const {      // group 0 of the last ode_run
+    if (!ode_ctl_.empty()) ode_stats_each(0, nullptr, accepted, rejected, t_accepted, cap, nullptr, nullptr);
+    else { if (accepted) *accepted = 0; if (rejected) *rejected = 0; }
   }
   void set_noise_streams(const unsigned long long* ids, int n) { streams_next_.assign(ids, ids + n); }
   void set_ragged_frames(const int* frames, int n) { set_frames(frames, n); }     // sgmse_set_frames
@@ -2343,14 +2190,12 @@ class Engine {
   float *temb_act_ = nullptr, *bias_table_ = nullptr, *step_table_ = nullptr, *tsteps_ = nullptr, *coef_table_ = nullptr; int temb_rows_ = 0;
   drt::graph_t graph_{}; bool graph_valid_ = false; GraphKey graph_key_{};
   int nfe_ = 0;
-  // adaptive ODE sampler (ode_sample): slopes K_0..K_6, stage input, scalar table, reduction buffers, the pinned result, last run's statistics
+  // adaptive ODE sampler (ode_run): slopes K_0..K_6, stage input; scalar table, reduction buffers and the pinned results for ode_cap_
+  // groups; last run's controllers (one per group) and round statistics
   float2* ode_k_[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float2* ode_xs_ = nullptr; size_t ode_n_ = 0;
-  double *ode_table_ = nullptr, *ode_partial_ = nullptr, *ode_result_ = nullptr, *ode_host_ = nullptr;
-  int ode_accepted_ = 0, ode_rejected_ = 0; std::vector<double> ode_t_acc_;
-  // per-utterance step control (ode_sample_each): table, reduction buffers and the pinned results for ode_each_cap_ utterances; last run's controllers
   static constexpr int kOdeEachMaxB = 1024;
-  double *ode_etable_ = nullptr, *ode_epartial_ = nullptr, *ode_eresult_ = nullptr, *ode_ehost_ = nullptr; int ode_each_cap_ = 0;
-  std::vector<OdeControl> ode_each_; int ode_rounds_ = 0, ode_wasted_ = 0;
+  double *ode_table_ = nullptr, *ode_partial_ = nullptr, *ode_result_ = nullptr, *ode_host_ = nullptr; int ode_cap_ = 0;
+  std::vector<OdeControl> ode_ctl_; int ode_rounds_ = 0, ode_wasted_ = 0;
   bool prof_ = false; std::vector<ProfRec> prof_recs_; size_t prof_used_ = 0; float prof_ms_[TC_COUNT]; double prof_flops_[TC_COUNT]; int prof_n_[TC_COUNT];
 };
 

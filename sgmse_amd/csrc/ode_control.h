@@ -1,7 +1,7 @@
 // Host side of the adaptive probability-flow sampler: scipy's RK45 step control (scipy/integrate/_ivp/rk.py RungeKutta._step_impl,
-// common.py select_initial_step) for ONE integration, in double.  Engine::ode_sample drives one controller for the whole flattened
-// batch, Engine::ode_sample_each one per utterance; both go through the code below and nothing else decides a step, so an utterance
-// integrated alone and the same utterance inside a batch take the same steps from the same norms.
+// common.py select_initial_step) for ONE integration, in double.  Engine::ode_run drives one controller per group: one for the whole
+// flattened batch, or one per utterance; nothing but the code below decides a step, so an utterance integrated alone and the same
+// utterance inside a batch take the same steps from the same norms.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -41,7 +41,7 @@ struct OdeControl {
   bool done() const { return !(dir * (t - t_stop) < 0); }
   double last_time(double t0) const { return t_accepted.empty() ? t0 : t_accepted.back(); }
 
-  // select_initial_step (Hairer, Norsett, Wanner I, II.4), error estimator order 4.  s0, s1: the sums of ode_init_norms_kernel.
+  // select_initial_step (Hairer, Norsett, Wanner I, II.4), error estimator order 4.  s0, s1: the sums of ode_init_norms_each_kernel.
   // First pass (x, K_0) -> the probe step h0: the probe evaluation is at t + h0 dir, its stage coefficient h0 dir.
   double probe_step(double s0, double s1) {
     const double d0 = std::sqrt(s0 / n);
@@ -84,7 +84,7 @@ struct OdeControl {
     for (int j = 0; j < 7; ++j) table[5 * stride + 1 + j] = h * E[j];
     table[6 * stride + 1] = h * A[1][0];
   }
-  // s0: the sum of ode_error_kernel.  True: accepted (t advanced, "first same as last": the caller makes x <- y_new, K_0 <- K_6).
+  // s0: the sum of ode_error_each_kernel.  True: accepted (t advanced, "first same as last": the caller makes x <- y_new, K_0 <- K_6).
   bool finish_attempt(double s0) {
     const double norm = std::sqrt(s0 / n);
     if (norm < 1.0) {

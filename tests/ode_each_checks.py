@@ -1,5 +1,5 @@
 """Checks of the native adaptive sampler's per-utterance step control (get_ode_sampler(solver="native", step_control="utterance") ->
-sgmse_ode_sample_each, sgmse_amd/csrc/kernels_ode_each.h), shared by the emulator and the GPU test modules.  The defining property:
+sgmse_ode_sample_each, sgmse_amd/csrc/kernels_ode.h with one controller group per utterance), shared by the emulator and the GPU test modules.  The defining property:
 utterance b of any batch, uniform or ragged, in any slot, is bit-identical to the existing solver's run on that utterance alone, with
 the same evaluation count, accepted / rejected counts and accepted time points."""
 import numpy as np

@@ -180,14 +180,32 @@ def check_scipy_default_unchanged(dev):
         m.get_ode_sampler(y, seed=3, **kw)
 
 
+def _dopri_step(m, dev, y, z, hh):
+    """One Dormand-Prince step of size hh from (t = 1, z), formed in complex128 from ScoreModel.forward-based drifts: (z, the end point)."""
+    C = [0.0, 1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0]
+    A = [[], [1 / 5], [3 / 40, 9 / 40], [44 / 45, -56 / 15, 32 / 9], [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
+         [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656]]
+    Bw = [35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84]
+    rsde = m.sde.copy().reverse(m, probability_flow=True)
+    f = lambda t, x: rsde.sde(x.type(torch.complex64), y, torch.ones(y.shape[0], device=dev) * t)[0].to(torch.complex128)
+    with torch.no_grad():
+        x = z.to(torch.complex128)
+        K = [f(1.0, x)]
+        for s in range(1, 6):
+            K.append(f(1.0 + C[s] * hh, x + sum(a * k for a, k in zip(A[s], K)) * hh))
+        return x, x + hh * sum(b * k for b, k in zip(Bw, K))
+
+
+V2_WRAP = dict(loss_type="denoiser", network_scaling="1/sigma", c_in="edm", c_out="1", c_skip="0", sigma_data=0.1)
+
+
 def check_v2_callback(dev):
     """ncsnpp_v2 ('denoiser', network scaling 1/sigma, c_in 'edm'): the host callback receives each attempt's six stage times, its rows
     reach the device table, and ONE attempted step (first_step given, a tolerance under which it is accepted) equals the
     Dormand-Prince step formed from ScoreModel.forward-based drifts at the same stage times, within the drift gate of
     check_ode_rk45 (1e-5) on the step's increment."""
     cfg = _small_cfg("ncsnpp_v2")
-    wrap = dict(loss_type="denoiser", network_scaling="1/sigma", c_in="edm", c_out="1", c_skip="0", sigma_data=0.1)
-    m, _ = make_model(cfg, dev, **wrap)
+    m, _ = make_model(cfg, dev, **V2_WRAP)
     y = synth.synth_spec(1, 64, 64, seed=4).to(dev)
     g = torch.Generator().manual_seed(3)
     z = (y.cpu() + 0.3 * torch.randn(y.shape, dtype=torch.complex64, generator=g)).to(dev)
@@ -211,24 +229,49 @@ def check_v2_callback(dev):
     want_t = [float(np.float32(1.0))] + [float(np.float32(1.0 + c * hh)) for c in C[1:5]] + [float(np.float32(1.0 + C[5] * hh)), float(np.float32(1.0 + hh))]
     got_t = [t for call in seen for t in call]
     assert got_t[1:8] == want_t, (got_t, want_t)      # (got_t[0]: the probe that asks whether the model has an affine wrapper)
-    # the step itself from ScoreModel.forward-based drifts
-    A = [[], [1 / 5], [3 / 40, 9 / 40], [44 / 45, -56 / 15, 32 / 9], [19372 / 6561, -25360 / 2187, 64448 / 6561, -212 / 729],
-         [9017 / 3168, -355 / 33, 46732 / 5247, 49 / 176, -5103 / 18656]]
-    Bw = [35 / 384, 0, 500 / 1113, 125 / 192, -2187 / 6784, 11 / 84]
-    rsde = m.sde.copy().reverse(m, probability_flow=True)
-    f = lambda t, x: rsde.sde(x.type(torch.complex64), y, torch.ones(1, device=dev) * t)[0].to(torch.complex128)
-    with torch.no_grad():
-        x = z.to(torch.complex128)
-        K = [f(1.0, x)]
-        for s in range(1, 6):
-            K.append(f(1.0 + C[s] * hh, x + sum(a * k for a, k in zip(A[s], K)) * hh))
-        want = x + hh * sum(b * k for b, k in zip(Bw, K))
+    x, want = _dopri_step(m, dev, y, z, hh)
     # the accepted state is not returned by a failed call: run the same single step to completion by integrating to eps = 1 - h
     out, nfe = m.get_ode_sampler(y, denoise=False, rtol=1e3, atol=1e3, solver="native", first_step=h, eps=0.9)(z=z)
     step = (want - x).cpu()
     err = rel_l2((out.to(torch.complex128) - x).cpu(), step)
     print(f"v2 wrapper on {dev}: one Dormand-Prince step of size {h}: increment rel_l2 vs ScoreModel.forward-based drifts = {err:.3e}")
     assert nfe == 7 and err < 1e-5, (nfe, err)
+
+
+def check_batch_control_step(dev):
+    """Batch control with MORE THAN ONE utterance on a network whose time-embedding rows matter: the construction of check_v2_callback
+    at B = 2 (the second utterance three times the first).  One accepted attempt under step_control="batch": 7 evaluations; the host
+    callback sees ONE time for the start and the SIX stage times of the attempt (one controller group: not 2 and 12); the increment
+    is within the one-step gate of check_v2_callback (1e-5, relative L2) of the Dormand-Prince step formed from ScoreModel.forward-
+    based drifts on the two-utterance batch."""
+    m, _ = make_model(_small_cfg("ncsnpp_v2"), dev, **V2_WRAP)
+    y = synth.synth_spec(2, 64, 64, seed=4)
+    y[1] *= 3.0
+    g = torch.Generator().manual_seed(3)
+    z = (y + 0.3 * torch.randn(y.shape, dtype=torch.complex64, generator=g)).to(dev)
+    y = y.to(dev)
+    h = 1.0 - 0.9
+    hh = (1.0 - h) - 1.0
+    seen = []
+    orig = m.score_affine
+
+    def spy(ts):
+        seen.append([float(v) for v in ts])
+        return orig(ts)
+    m.score_affine = spy
+    try:
+        out, nfe = m.get_ode_sampler(y, denoise=False, rtol=1e3, atol=1e3, solver="native", step_control="batch", first_step=h, eps=0.9)(z=z)
+    finally:
+        m.score_affine = orig
+    C = [1 / 5, 3 / 10, 4 / 5, 8 / 9, 1.0]
+    stage_t = [float(np.float32(1.0 + c * hh)) for c in C[:4]] + [float(np.float32(1.0 + C[4] * hh)), float(np.float32(1.0 + hh))]
+    assert nfe == 7, nfe
+    assert seen[1:] == [[1.0], stage_t], (seen, stage_t)       # (seen[0]: the probe that asks whether the model has an affine wrapper)
+    x, want = _dopri_step(m, dev, y, z, hh)
+    err = rel_l2((out.to(torch.complex128) - x).cpu(), (want - x).cpu())
+    print(f"batch control, two utterances, v2 wrapper on {dev}: one Dormand-Prince step of size {h}: increment rel_l2 vs "
+          f"ScoreModel.forward-based drifts = {err:.3e}")
+    assert err < 1e-5, err
 
 
 def check_enhancement_flag(dev):

@@ -1,5 +1,5 @@
 """Per-utterance step control of the native adaptive sampler (get_ode_sampler(solver="native", step_control="utterance"),
-sgmse_amd/csrc/kernels_ode_each.h) on the CPU workgroup emulator.  The emulator takes seconds per evaluation: the closed-form cases run
+sgmse_amd/csrc/kernels_ode.h) on the CPU workgroup emulator.  The emulator takes seconds per evaluation: the closed-form cases run
 in full on the zero-score network, the bit-identity cases with the quick settings of ode_each_checks (one half-interval attempt on the
 random-weight network; the round that one utterance accepts and the other rejects on the zero-score network)."""
 import os

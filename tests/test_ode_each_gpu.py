@@ -1,5 +1,5 @@
 """Per-utterance step control of the native adaptive sampler (get_ode_sampler(solver="native", step_control="utterance"),
-sgmse_amd/csrc/kernels_ode_each.h) on the hardware."""
+sgmse_amd/csrc/kernels_ode.h) on the hardware."""
 import pytest
 
 import ode_each_checks as K

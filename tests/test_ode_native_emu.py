@@ -34,5 +34,9 @@ def test_native_rk45_score_wrapper_callback_of_v2_models(emu):
     K.check_v2_callback(emu)
 
 
+def test_native_rk45_batch_control_of_two_utterances(emu):
+    K.check_batch_control_step(emu)
+
+
 def test_enhancement_ode_solver_flag(emu):
     K.check_enhancement_flag(emu)

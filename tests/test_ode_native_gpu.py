@@ -38,5 +38,9 @@ def test_native_rk45_score_wrapper_callback_of_v2_models(hip):
     K.check_v2_callback(hip)
 
 
+def test_native_rk45_batch_control_of_two_utterances(hip):
+    K.check_batch_control_step(hip)
+
+
 def test_enhancement_ode_solver_flag(hip):
     K.check_enhancement_flag(hip)
