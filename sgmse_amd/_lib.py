@@ -160,6 +160,22 @@ def _ragged_geometry(items, planes: int, what: str):
     return frames, F_
 
 
+def _unpack_ragged(out: torch.Tensor, frames, F_: int):
+    """The packed result of a ragged call as one [1,F,T_b] tensor per utterance."""
+    outs, o = [], 0
+    for T_b in frames:
+        outs.append(out[o:o + F_ * T_b].reshape(1, F_, T_b))
+        o += F_ * T_b
+    return outs
+
+
+def _host_rows(affine, N: int):
+    """The score wrapper's (in_scale, score_alpha, score_beta) as fp32 host arrays of length N each; three None without a wrapper."""
+    if affine is None:
+        return [None, None, None]
+    return [torch.as_tensor(v, dtype=torch.float32).detach().to("cpu").expand(N).contiguous() for v in affine]
+
+
 class Context:
     """One sgmse_ctx: a device, a stream, the weights and the activation arena."""
 
@@ -206,6 +222,40 @@ class Context:
         if rc == -1:
             raise ValueError(msg)
         raise RuntimeError(f"sgmse_hip error {rc}: {msg}")
+
+    def _get_int(self, fn, ctype=_I) -> int:
+        """``fn(ctx, &out)`` of the C ABI: the integer it writes."""
+        out = ctype(0)
+        self.check(fn(self.h, C.byref(out)))
+        return out.value
+
+    def _pack_ragged(self, items, planes: int, what: str):
+        """A ragged batch (list of [planes,F,T_b] tensors, see set_frames) as the library takes it: (utterance after utterance in one
+        flat complex64 tensor, the frame counts, F)."""
+        frames, F_ = _ragged_geometry(items, planes, what)
+        return torch.cat([check_tensor(v, what, torch.complex64, self.device).reshape(-1) for v in items]), frames, F_
+
+    def _take_streams(self, streams, B: int) -> None:
+        """``streams`` of a sampler call (None: the default ids): checked against the batch and handed to the library."""
+        if streams is not None:
+            if len(streams) != B:
+                raise ValueError(f"streams must name the {B} utterances of the batch, got {len(streams)}")
+            self.set_noise_streams(streams)
+
+    def _with_capturable_stream(self, run, use_graph) -> None:
+        """``run()`` on the current stream, or, when it is to capture a graph there and cannot, on a side stream ordered with it."""
+        cur = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
+        if cur is not None and use_graph and cur.cuda_stream == 0:
+            # stream capture is not allowed on the legacy default stream: run the sampler on a side stream
+            side = self._keep.get("side_stream")
+            if side is None:
+                side = self._keep["side_stream"] = torch.cuda.Stream(self.device)
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                run()
+            cur.wait_stream(side)
+        else:
+            run()
 
     def use_current_stream(self):
         if self.device.type == "cuda":
@@ -263,9 +313,7 @@ class Context:
             self.sync()
 
     def param_count(self) -> int:
-        out = _LL(0)
-        self.check(self.lib.sgmse_param_count(self.h, C.byref(out)))
-        return out.value
+        return self._get_int(self.lib.sgmse_param_count, _LL)
 
     def forward(self, xy: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
         """NCSNpp.forward: xy complex64 [B,2,F,T], t float32 [B] -> complex64 [B,1,F,T]."""
@@ -291,9 +339,9 @@ class Context:
         if isinstance(Y, (list, tuple)):       # ragged batch: utterances [F,T_b] (or [1,F,T_b]) of different lengths, see set_frames
             if noise is not None:
                 raise ValueError("ragged batches use in-kernel noise only")
-            frames, F_ = _ragged_geometry(Y, 1, "y")
-            B, T = len(Y), max(frames)
-            Y = torch.cat([check_tensor(y, "y", torch.complex64, self.device).reshape(-1) for y in Y])
+            B = len(Y)
+            Y, frames, F_ = self._pack_ragged(Y, 1, "y")
+            T = max(frames)
         else:
             Y = check_tensor(Y, "y", torch.complex64, self.device)
             if Y.dim() != 4 or Y.shape[1] != 1:
@@ -314,8 +362,7 @@ class Context:
             keep[k] = v
             setattr(cfg, k, C.cast(v.data_ptr(), C.POINTER(C.c_float)))
         if affine is not None:
-            for k, v in zip(("in_scale", "score_alpha", "score_beta"), affine):
-                v = torch.as_tensor(v, dtype=torch.float32).detach().to("cpu").expand(N).contiguous()
+            for k, v in zip(("in_scale", "score_alpha", "score_beta"), _host_rows(affine, N)):
                 keep[k] = v
                 setattr(cfg, k, C.cast(v.data_ptr(), C.POINTER(C.c_float)))
         if noise is not None:
@@ -326,10 +373,7 @@ class Context:
                 raise ValueError(f"noise must be [{need},{B},1,{F_},{T}] complex64, got {tuple(noise.shape)}")
         out = torch.empty_like(Y)
         nfe = _I(0)
-        if streams is not None:
-            if len(streams) != B:
-                raise ValueError(f"streams must name the {B} utterances of the batch, got {len(streams)}")
-            self.set_noise_streams(streams)
+        self._take_streams(streams, B)
 
         def run():
             self.use_current_stream()
@@ -339,26 +383,9 @@ class Context:
             self.check(self.lib.sgmse_pc_sample(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, C.byref(cfg), ptr(noise),
                                                 C.c_ulonglong(seed & (2 ** 64 - 1)), C.byref(nfe)))
 
-        cur = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
-        if cur is not None and use_graph and cur.cuda_stream == 0:
-            # stream capture is not allowed on the legacy default stream: run the sampler on a side stream
-            side = self._keep.get("side_stream")
-            if side is None:
-                side = self._keep["side_stream"] = torch.cuda.Stream(self.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                run()
-            cur.wait_stream(side)
-        else:
-            run()
+        self._with_capturable_stream(run, use_graph)
         self._keep["sampler"] = (noise, keep)   # the captured graph refers to the replayed-noise buffer
-        if frames is not None:                  # unpack: one [1,F,T_b] tensor per utterance
-            outs, o = [], 0
-            for T_b in frames:
-                outs.append(out[o:o + F_ * T_b].reshape(1, F_, T_b))
-                o += F_ * T_b
-            return outs, nfe.value
-        return out, nfe.value
+        return (out if frames is None else _unpack_ragged(out, frames, F_)), nfe.value
 
     def sb_sample(self, Y: torch.Tensor, table: Dict[str, torch.Tensor], *, stochastic: bool, noise: Optional[torch.Tensor],
                   seed: int, affine=None, use_graph: bool = True, streams=None):
@@ -368,19 +395,14 @@ class Context:
         N = int(table["t"].numel())
         fp = lambda v: C.cast(v.data_ptr(), C.POINTER(_F))
         keep = [table[k].detach().to("cpu", torch.float32).contiguous() for k in ("t", "w_prev", "w_est", "w_y", "w_z")]
-        aff = [None, None, None]
-        if affine is not None:
-            aff = [torch.as_tensor(v, dtype=torch.float32).detach().to("cpu").expand(N).contiguous() for v in affine]
+        aff = _host_rows(affine, N)
         if noise is not None:
             noise = check_tensor(noise, "noise", torch.complex64, self.device)
             if noise.shape[0] < N or tuple(noise.shape[1:]) != tuple(Y.shape):
                 raise ValueError(f"noise must be [{N},{B},1,{F_},{T}] complex64, got {tuple(noise.shape)}")
         out = torch.empty_like(Y)
         nfe = _I(0)
-        if streams is not None:
-            if len(streams) != B:
-                raise ValueError(f"streams must name the {B} utterances of the batch, got {len(streams)}")
-            self.set_noise_streams(streams)
+        self._take_streams(streams, B)
 
         def run():
             self.use_current_stream()
@@ -389,17 +411,7 @@ class Context:
                                                 *[None if v is None else fp(v) for v in aff], int(bool(stochastic)), ptr(noise),
                                                 C.c_ulonglong(seed & (2 ** 64 - 1)), int(bool(use_graph)), C.byref(nfe)))
 
-        cur = torch.cuda.current_stream(self.device) if self.device.type == "cuda" else None
-        if cur is not None and use_graph and cur.cuda_stream == 0:
-            side = self._keep.get("side_stream")
-            if side is None:
-                side = self._keep["side_stream"] = torch.cuda.Stream(self.device)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                run()
-            cur.wait_stream(side)
-        else:
-            run()
+        self._with_capturable_stream(run, use_graph)
         self._keep["sb"] = (noise, keep, aff)
         return out, nfe.value
 
@@ -458,10 +470,7 @@ class Context:
         a rectangular one; ``groups``: controllers of the run, what ode_stats_each will list): (out, nfe).  An exception of the host
         callback is raised again here; a failed run raises RuntimeError."""
         cfg, failure, cb = self._ode_cfg(values, affine_fn)
-        if streams is not None:
-            if len(streams) != B:
-                raise ValueError(f"streams must name the {B} utterances of the batch, got {len(streams)}")
-            self.set_noise_streams(streams)
+        self._take_streams(streams, B)
         out = torch.empty_like(Y)
         nfe = _I(0)
         self.use_current_stream()
@@ -505,19 +514,14 @@ class Context:
             return self._ode_call(self.lib.sgmse_ode_sample_each, Y, B, F_, T, [], B, values, noise, x0, seed, streams, affine_fn)
         if noise is not None:
             raise ValueError("ragged batches take the prior from seed / streams or a start state z, not from replayed noise")
-        frames, F_ = _ragged_geometry(Y, 1, "y")
-        B, T = len(Y), max(frames)
-        Y = torch.cat([check_tensor(y, "y", torch.complex64, self.device).reshape(-1) for y in Y])
+        B = len(Y)
+        Y, frames, F_ = self._pack_ragged(Y, 1, "y")
         if x0 is not None:
             if not isinstance(x0, (list, tuple)) or len(x0) != B or _ragged_geometry(x0, 1, "z") != (frames, F_):
                 raise ValueError("the start state of a ragged batch is a list with the shapes of y's utterances")
-            x0 = torch.cat([check_tensor(x, "z", torch.complex64, self.device).reshape(-1) for x in x0])
-        out, nfe = self._ode_call(self.lib.sgmse_ode_sample_each, Y, B, F_, T, frames, B, values, None, x0, seed, streams, affine_fn)
-        outs, o = [], 0                         # unpack: one [1,F,T_b] tensor per utterance
-        for T_b in frames:
-            outs.append(out[o:o + F_ * T_b].reshape(1, F_, T_b))
-            o += F_ * T_b
-        return outs, nfe
+            x0 = self._pack_ragged(x0, 1, "z")[0]
+        out, nfe = self._ode_call(self.lib.sgmse_ode_sample_each, Y, B, F_, max(frames), frames, B, values, None, x0, seed, streams, affine_fn)
+        return _unpack_ragged(out, frames, F_), nfe
 
     def ode_stats_each(self):
         """The last ``ode_sample(step_control="utterance")`` run: dict(utterances=[dict(nfe=..., accepted=..., rejected=...,
@@ -547,9 +551,9 @@ class Context:
         t = check_tensor(t, "t", torch.float32, self.device)
         frames = []
         if isinstance(xy, (list, tuple)):
-            frames, F_ = _ragged_geometry(xy, 2, "x")
-            B, T = len(xy), max(frames)
-            xy = torch.cat([check_tensor(x, "x", torch.complex64, self.device).reshape(-1) for x in xy])
+            B = len(xy)
+            xy, frames, F_ = self._pack_ragged(xy, 2, "x")
+            T = max(frames)
             out = torch.empty(F_ * sum(frames), dtype=torch.complex64, device=self.device)
         else:
             xy = check_tensor(xy, "x", torch.complex64, self.device)
@@ -579,15 +583,11 @@ class Context:
 
     def conv_winograd(self) -> bool:
         """True when the wide levels' 3x3 layers run on the Winograd F(2,3) x fp16x2 kernel (kernels_conv_wino.h)."""
-        out = C.c_int(0)
-        self.check(self.lib.sgmse_conv_winograd(self.h, C.byref(out)))
-        return bool(out.value)
+        return bool(self._get_int(self.lib.sgmse_conv_winograd))
 
     def conv_split_mode(self) -> int:
         """0: fp32 MFMA, 1: bf16x3 split, 2: fp16x2 split on the wide 3x3 layers (kernels_conv_split.h)."""
-        out = C.c_int(0)
-        self.check(self.lib.sgmse_conv_split_mode(self.h, C.byref(out)))
-        return out.value
+        return self._get_int(self.lib.sgmse_conv_split_mode)
 
     def set_noise_streams(self, ids) -> None:
         """Noise-stream ids (one per utterance) for the next sampler call with in-kernel noise: see sgmse_set_noise_streams."""
@@ -607,8 +607,7 @@ class Context:
     def forward_ragged(self, xys, t: torch.Tensor):
         """NCSNpp.forward on utterances of different lengths in ONE batch: xys = list of complex64 [2,F,T_b]; returns the list of
         complex64 [1,F,T_b], each bit-identical to ``forward(xy[None], t[b:b+1])[0]``."""
-        frames, F_ = _ragged_geometry(xys, 2, "x")
-        packed = torch.cat([check_tensor(x, "x", torch.complex64, self.device).reshape(-1) for x in xys])
+        packed, frames, F_ = self._pack_ragged(xys, 2, "x")
         t = check_tensor(t.reshape(-1), "time_cond", torch.float32, self.device)
         if t.numel() != len(xys):
             raise ValueError("time_cond must have one entry per utterance")
@@ -616,25 +615,15 @@ class Context:
         self.set_frames(frames)
         self.use_current_stream()
         self.check(self.lib.sgmse_ncsnpp_forward(self.h, packed.data_ptr(), t.data_ptr(), out.data_ptr(), len(xys), F_, max(frames)))
-        outs, o = [], 0
-        for T_b in frames:
-            outs.append(out[o:o + F_ * T_b].reshape(1, F_, T_b))
-            o += F_ * T_b
-        return outs
+        return _unpack_ragged(out, frames, F_)
 
     def graph_captures(self) -> int:
         """Number of hipGraph captures (+ instantiations) of a sampler step this context has done."""
-        out = _I(0)
-        self.check(self.lib.sgmse_graph_captures(self.h, C.byref(out)))
-        return out.value
+        return self._get_int(self.lib.sgmse_graph_captures)
 
     def graph_updates(self) -> int:
         """Number of times a captured step was updated in place (hipGraphExecUpdate) instead of being instantiated anew."""
-        out = _I(0)
-        self.check(self.lib.sgmse_graph_updates(self.h, C.byref(out)))
-        return out.value
+        return self._get_int(self.lib.sgmse_graph_updates)
 
     def arena_bytes(self) -> int:
-        out = _LL(0)
-        self.check(self.lib.sgmse_arena_bytes(self.h, C.byref(out)))
-        return out.value
+        return self._get_int(self.lib.sgmse_arena_bytes, _LL)

@@ -27,14 +27,7 @@ int sg_guard(sgmse_ctx* ctx, Fn&& fn) {
 }
 #define SG_ARG(ctx, cond, msg) do { if (!(cond)) { if (ctx) (ctx)->err = std::string("invalid argument: ") + msg; return SGMSE_EINVAL; } } while (0)
 
-// sgmse_ode_sample / sgmse_ode_sample_each: the argument checks, sgmse_ode_cfg -> OdeCfg, the run; *nfe also after a failed run
-static sgmse::OdeCfg sg_ode_cfg(const sgmse_ode_cfg* cfg) {
-  sgmse::OdeCfg o;
-  o.theta = cfg->theta; o.sigma_min = cfg->sigma_min; o.sigma_max = cfg->sigma_max; o.std1 = cfg->std1;
-  o.t_end = cfg->t_end; o.eps = cfg->eps; o.rtol = cfg->rtol; o.atol = cfg->atol; o.first_step = cfg->first_step;
-  o.max_step = cfg->max_step; o.max_nfe = cfg->max_nfe; o.coef_fn = cfg->coef_fn; o.coef_user = cfg->coef_user;
-  return o;
-}
+// sgmse_ode_sample / sgmse_ode_sample_each: the argument checks, the run; *nfe also after a failed run
 static int sg_ode_run(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int T, const sgmse_ode_cfg* cfg, const void* noise,
                       const void* x0, unsigned long long seed, int* nfe, bool per_utterance) {
   SG_ARG(ctx, Y && out && cfg && B > 0 && F > 0 && T > 0, "null pointer or non-positive shape");
@@ -43,7 +36,7 @@ static int sg_ode_run(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, in
   SG_ARG(ctx, cfg->max_nfe >= 1, "max_nfe must be >= 1");
   SG_ARG(ctx, !(noise && x0), "give replayed noise or a start state, not both");
   return sg_guard(ctx, [&](sgmse::Engine& e) {
-    try { e.ode_run((const float2*)Y, (float2*)out, B, F, T, sg_ode_cfg(cfg), (const float2*)noise, (const float2*)x0, seed, per_utterance); }
+    try { e.ode_run((const float2*)Y, (float2*)out, B, F, T, *cfg, (const float2*)noise, (const float2*)x0, seed, per_utterance); }
     catch (...) { if (nfe) *nfe = e.last_nfe(); throw; }
     if (nfe) *nfe = e.last_nfe();
   });
@@ -121,14 +114,7 @@ int sgmse_pc_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int 
   SG_ARG(ctx, cfg->predictor == 0 || cfg->predictor == 1, "predictor must be none or reverse_diffusion");
   SG_ARG(ctx, cfg->corrector == 0 || cfg->corrector_steps >= 1, "corrector_steps must be >= 1");
   return sg_guard(ctx, [&](sgmse::Engine& e) {
-    sgmse::SamplerCfg s;
-    s.N = cfg->N; s.corrector = cfg->corrector; s.corrector_steps = cfg->corrector_steps; s.predictor = cfg->predictor;
-    s.probability_flow = cfg->probability_flow; s.denoise = cfg->denoise; s.theta = cfg->theta; s.std1 = cfg->std1;
-    s.t = cfg->t; s.dt = cfg->dt; s.ald_eps = cfg->ald_eps; s.ald_noise = cfg->ald_noise; s.G = cfg->G; s.G2 = cfg->G2;
-    s.snr = cfg->snr;
-    s.in_scale = cfg->in_scale; s.score_alpha = cfg->score_alpha; s.score_beta = cfg->score_beta;
-    s.use_graph = cfg->use_graph;
-    e.pc_sample((const float2*)Y, (float2*)out, B, F, T, s, (const float2*)noise, seed);
+    e.pc_sample((const float2*)Y, (float2*)out, B, F, T, *cfg, (const float2*)noise, seed);
     if (nfe) *nfe = e.last_nfe();
   });
 }

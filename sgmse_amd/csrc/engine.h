@@ -22,6 +22,7 @@
 #include "kernels_ode.h"
 #include "ode_control.h"
 #include "kernels_stft.h"
+#include "../../include/sgmse_hip.h"     // sgmse_sampler_cfg, sgmse_ode_cfg: the samplers take the public structs
 
 namespace sgmse {
 
@@ -302,37 +303,6 @@ struct ConvW {            // one convolution's parameters on the device
 struct ResW { const float *g0w, *g0b, *g1w, *g1b; ConvW c0, c1, c2; bool has_c2; int temb_off; };
 struct AttnW { const float *gw, *gb; ConvW qkv, proj; };
 
-struct SamplerCfg {
-  int N = 30;
-  int corrector = 1;        // 0 none, 1 ald, 2 langevin
-  float snr = 0.f;          // langevin only (ALD's snr is folded into the step table)
-  int corrector_steps = 1;
-  int predictor = 1;        // 0 none, 1 reverse_diffusion
-  int probability_flow = 0;
-  int denoise = 1;
-  float theta = 1.5f;
-  float std1 = 0.f;         // OUVE._std(T)
-  const float* t = nullptr; const float* dt = nullptr; const float* ald_eps = nullptr; const float* ald_noise = nullptr;
-  const float* G = nullptr; const float* G2 = nullptr;   // host arrays [N]
-  // score wrapper per step (host arrays [N], all three or none): network input scale, score = alpha*x_t + beta*F
-  const float* in_scale = nullptr; const float* score_alpha = nullptr; const float* score_beta = nullptr;
-  int use_graph = 1;
-};
-
-// Engine::ode_run (adaptive probability-flow sampler, kernels_ode.h)
-struct OdeCfg {
-  float theta = 1.5f, sigma_min = 0.05f, sigma_max = 0.5f;
-  float std1 = 0.f;                       // OUVE._std(T) for the prior draw
-  double t_end = 1.0, eps = 0.03;          // integrate from t_end (sde.T) to eps
-  double rtol = 1e-5, atol = 1e-5;
-  double first_step = 0.0, max_step = 0.0; // 0: select_initial_step / no limit
-  int max_nfe = 100000;                    // more evaluations than this is an error
-  // score wrapper of ncsnpp_v2 models at the solver's stage times (null: old-code branch, score = -F): called once per attempted
-  // step with that attempt's n stage times (fp32, as the network sees them); fills gamma / alpha / beta [n]
-  void (*coef_fn)(void* user, int n, const float* t, float* gamma, float* alpha, float* beta) = nullptr;
-  void* coef_user = nullptr;
-};
-
 class Engine {
  public:
   explicit Engine(int device, void* stream) : device_(device) {
@@ -344,9 +314,7 @@ class Engine {
     for (void* p : owned_) drt::free_dev(p);
     for (void* p : wowned_) drt::free_dev(p);
     if (graph_valid_ || graph_stale_) drt::graph_destroy(&graph_);
-    if (hstage_) drt::free_host(hstage_);
     if (ode_host_) drt::free_host(ode_host_);
-    if (hstage_ev_init_) drt::event_destroy(&hstage_ev_);
     for (drt::event_t& e : side_ev_) drt::event_destroy(&e);
     if (side_stream_ready_) drt::stream_destroy(side_stream_);
     for (ProfRec& r : prof_recs_) { drt::event_destroy(&r.a); drt::event_destroy(&r.b); }
@@ -419,7 +387,62 @@ class Engine {
   }
 
   // ---- sampler --------------------------------------------------------------------------------------------------
-  void pc_sample(const float2* Y, float2* out, int B, int F, int T, const SamplerCfg& sc, const float2* noise,
+  // what a captured step depends on.  The Philox seed is NOT part of it: the sampler kernels read it from a device word
+  // (upload_tables), so one capture serves every utterance / batch of a run (the Python samplers draw a fresh seed per call)
+  struct GraphKey {
+    int B, F, T, corr, ncorr, pred, pf; const void* y; const void* noise; float theta; int dps;
+    bool operator==(const GraphKey& o) const {
+      return B == o.B && F == o.F && T == o.T && corr == o.corr && ncorr == o.ncorr && pred == o.pred && pf == o.pf && y == o.y &&
+             noise == o.noise && theta == o.theta && dps == o.dps;
+    }
+  };
+  // What the fixed-step samplers share in front of their loop.  fill(i, row) writes step i's row of the step table (row[SC_T] = its
+  // time); in_scale / alpha / beta are the score wrapper's host arrays [N], all three or none.  Tables and seed -> device (no host
+  // synchronisation: pinned staging), time embeddings of the N steps, y -> the engine-owned copy (a captured graph never refers to
+  // caller memory).  Returns the device seed words and the network's control block; ctl.coef is set iff the wrapper was given.
+  struct StepSetup { const unsigned long long* seed; FwdCtl ctl; };
+  template <class Fill>
+  StepSetup begin_steps(const char* who, const float2* Y, size_t n, int B, int N, unsigned long long seed, Fill&& fill,
+                        const float* in_scale, const float* alpha, const float* beta) {
+    std::vector<float> tab((size_t)N * SC_STRIDE, 0.f), tv(N), cf;
+    for (int i = 0; i < N; ++i) { float* r = &tab[(size_t)i * SC_STRIDE]; fill(i, r); tv[i] = r[SC_T]; }
+    const bool affine = in_scale && alpha && beta;
+    SG_REQUIRE(affine || (!in_scale && !alpha && !beta), std::string(who) + ": give all three score-wrapper arrays or none");
+    if (affine) {
+      cf.assign((size_t)N * 4, 0.f);
+      for (int i = 0; i < N; ++i) { cf[4 * i] = in_scale[i]; cf[4 * i + 1] = alpha[i]; cf[4 * i + 2] = beta[i]; }
+    }
+    const unsigned long long* seed_dev = upload_tables(tab, tv, cf, seed, B);
+    compute_temb(tsteps_, N);
+    SG_CHECK(drt::memcpy_d2d(sy_, Y, n * 8, stream_));
+    FwdCtl ctl{bias_table_, 0, tot_temb_, step_ctr_, tsteps_, 0, 1, -1.0f};
+    if (affine) { ctl.coef = coef_table_; ctl.coef_bstride = 0; ctl.coef_sstride = 1; }
+    return {seed_dev, ctl};
+  }
+  // N times the step `body`: as replays of the engine's ONE captured graph (captured anew, or updated in place, when `key` is not the
+  // captured step's), or eagerly
+  template <class Body>
+  void run_steps(int N, const GraphKey& key, bool use_graph, Body&& body) {
+    if (use_graph && drt::graphs_supported()) {
+      if (!graph_valid_ || !(key == graph_key_)) {
+        invalidate_graph();
+        capture_step(body);
+        graph_key_ = key;
+      }
+      for (int i = 0; i < N; ++i) SG_CHECK(drt::graph_launch(&graph_, stream_));
+    } else {
+      for (int i = 0; i < N; ++i) body();
+    }
+  }
+  // prior: sx_ = sy_ + std1 z over the n packed elements, z = noise (replayed, draw 0) or the Philox stream of the seed words
+  void draw_prior(const float2* noise, const unsigned long long* seed_dev, float std1, size_t n, int B, int per) {
+    SamplerArgs sa{};
+    sa.x = sx_; sa.y = sy_; sa.noise = noise; sa.seed = seed_dev; sa.std1 = std1; sa.n = (int)n; sa.B = B; sa.per = per;
+    sa.rag_off = ragged() ? rag_off_dev_[0] : nullptr;
+    DRT_LAUNCH(sampler_prior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), stream_, sa);
+  }
+
+  void pc_sample(const float2* Y, float2* out, int B, int F, int T, const sgmse_sampler_cfg& sc, const float2* noise,
                  unsigned long long seed) {
     require_ready();
     SG_REQUIRE(sc.N >= 1 && sc.t && sc.dt && sc.G && sc.G2, "pc_sample: step table missing");
@@ -428,50 +451,33 @@ class Engine {
     SG_REQUIRE(!ragged() || sc.corrector != 2, "ragged batches: the Langevin corrector couples the utterances of a batch (correctors.py:50-52) and is not supported");
     SG_REQUIRE(!ragged() || !noise, "ragged batches: replayed noise is not supported (in-kernel noise only)");
     const size_t n = ragged() ? rag_pix_[0] : (size_t)B * F * T;     // complex elements of Y / the result, utterance after utterance
-    // step table -> device
-    std::vector<float> tab((size_t)sc.N * SC_STRIDE, 0.f), tv(sc.N);
-    for (int i = 0; i < sc.N; ++i) {
-      float* r = &tab[(size_t)i * SC_STRIDE];
+    const StepSetup st = begin_steps("pc_sample", Y, n, B, sc.N, seed, [&](int i, float* r) {
       r[SC_T] = sc.t[i]; r[SC_DT] = sc.dt[i]; r[SC_G] = sc.G[i]; r[SC_G2] = sc.G2[i];
       if (sc.corrector == 1) { r[SC_ALD_EPS] = sc.ald_eps[i]; r[SC_ALD_NOISE] = sc.ald_noise[i]; }
-      tv[i] = sc.t[i];
-    }
-    const bool affine = sc.in_scale && sc.score_alpha && sc.score_beta;
-    SG_REQUIRE(affine || (!sc.in_scale && !sc.score_alpha && !sc.score_beta), "pc_sample: give all three score-wrapper arrays or none");
-    std::vector<float> cf;
-    if (affine) {
-      cf.assign((size_t)sc.N * 4, 0.f);
-      for (int i = 0; i < sc.N; ++i) { cf[4 * i] = sc.in_scale[i]; cf[4 * i + 1] = sc.score_alpha[i]; cf[4 * i + 2] = sc.score_beta[i]; }
-    }
-    const unsigned long long* seed_dev = upload_tables(tab, tv, cf, seed, B);      // no host synchronisation (pinned staging)
-    compute_temb(tsteps_, sc.N);
+    }, sc.in_scale, sc.score_alpha, sc.score_beta);
+    const FwdCtl& ctl = st.ctl;
 
     const int ncorr = sc.corrector ? sc.corrector_steps : 0;
     const bool pred_noise = sc.predictor == 1 && !sc.probability_flow;
     const int draws_per_step = ncorr + (pred_noise ? 1 : 0);
 
-    SG_CHECK(drt::memcpy_d2d(sy_, Y, n * 8, stream_));   // engine-owned copy: the captured graph never refers to caller memory
-    Y = sy_;
     SamplerArgs sa{};
-    sa.x = sx_; sa.x_mean = sxm_; sa.y = Y; sa.score = sscore_; sa.noise = noise; sa.seed = seed_dev;
+    sa.x = sx_; sa.x_mean = sxm_; sa.y = sy_; sa.score = sscore_; sa.noise = noise; sa.seed = st.seed;
     sa.table = step_table_; sa.step_ptr = step_ctr_; sa.theta = sc.theta; sa.std1 = sc.std1; sa.n = (int)n;
     sa.score_w = sc.probability_flow ? 0.5f : 1.0f;
     sa.snr = sc.snr; sa.B = B; sa.per = F * T; sa.partial = lang_partial_; sa.lang = lang_scal_;
     sa.rag_off = ragged() ? rag_off_dev_[0] : nullptr;
     const dim3 eg((unsigned)((n + 255) / 256));
 
-    sa.draw_base = 0; sa.draw_per_step = 0;
-    DRT_LAUNCH(sampler_prior_kernel, eg, dim3(256), stream_, sa);
+    draw_prior(noise, st.seed, sc.std1, n, B, F * T);
     SG_CHECK(drt::memcpy_d2d(sxm_, sx_, n * 8, stream_));
     DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_, 0);
 
-    FwdCtl ctl{bias_table_, 0, tot_temb_, step_ctr_, tsteps_, 0, 1, -1.0f};
-    if (affine) { ctl.coef = coef_table_; ctl.coef_bstride = 0; ctl.coef_sstride = 1; }
     const long long FT = ragged() ? 1 : (long long)F * T;          // batch stride of x / y (ragged: multiplier of the utterance's offset)
     auto step_body = [&]() {
       for (int cs = 0; cs < ncorr; ++cs) {
         arena_.reset();
-        run_forward(sx_, FT, Y, FT, sscore_, B, F, T, ctl);
+        run_forward(sx_, FT, sy_, FT, sscore_, B, F, T, ctl);
         SamplerArgs a = sa; a.draw_base = 1 + cs; a.draw_per_step = draws_per_step;
         if (sc.corrector == 2) {
           DRT_LAUNCH(sampler_langevin_norms_kernel, dim3(LANG_NBLK, B), dim3(256), stream_, a);
@@ -483,7 +489,7 @@ class Engine {
       }
       if (sc.predictor == 1) {
         arena_.reset();
-        run_forward(sx_, FT, Y, FT, sscore_, B, F, T, ctl);
+        run_forward(sx_, FT, sy_, FT, sscore_, B, F, T, ctl);
         SamplerArgs a = sa; a.draw_base = 1 + ncorr; a.draw_per_step = draws_per_step; a.add_noise = pred_noise ? 1 : 0;
         DRT_LAUNCH(sampler_revdiff_kernel, eg, dim3(256), stream_, a);
       }
@@ -491,20 +497,9 @@ class Engine {
       if (sc.predictor == 0 && ncorr > 0) SG_CHECK(drt::memcpy_d2d(sxm_, sx_, n * 8, stream_));
       DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
     };
-
-    GraphKey key{B, F, T, sc.corrector, ncorr, sc.predictor, sc.probability_flow + (affine ? 2 : 0), (const void*)Y, (const void*)noise,
-                 sc.theta + 1000.f * sc.snr * (sc.corrector == 2), draws_per_step};      // (set_frames invalidates the graph itself)
-    const bool want_graph = sc.use_graph && drt::graphs_supported();
-    if (want_graph) {
-      if (!graph_valid_ || !(key == graph_key_)) {
-        invalidate_graph();
-        capture_step(step_body);
-        graph_key_ = key;
-      }
-      for (int i = 0; i < sc.N; ++i) SG_CHECK(drt::graph_launch(&graph_, stream_));
-    } else {
-      for (int i = 0; i < sc.N; ++i) step_body();
-    }
+    run_steps(sc.N, GraphKey{B, F, T, sc.corrector, ncorr, sc.predictor, sc.probability_flow + (ctl.coef ? 2 : 0), (const void*)sy_, (const void*)noise,
+                             sc.theta + 1000.f * sc.snr * (sc.corrector == 2), draws_per_step},      // (set_frames invalidates the graph itself)
+              sc.use_graph, step_body);
     SG_CHECK(drt::memcpy_d2d(out, sc.denoise ? sxm_ : sx_, n * 8, stream_));
     nfe_ = sc.N * (ncorr + 1);   // the reference counts N*(corrector.n_steps+1) whatever the predictor (sampling/__init__.py:67)
   }
@@ -518,32 +513,18 @@ class Engine {
     SG_REQUIRE(!ragged(), "ragged batches: not supported by the Schroedinger-bridge sampler");
     ensure_shape(B, F, T, N);
     const size_t n = (size_t)B * F * T;
-    std::vector<float> tab((size_t)N * SC_STRIDE, 0.f), tv(N);
-    for (int i = 0; i < N; ++i) {
-      float* r = &tab[(size_t)i * SC_STRIDE];
+    const StepSetup st = begin_steps("sb_sample", Y, n, B, N, seed, [&](int i, float* r) {
       r[SC_T] = t[i]; r[SB_WPREV] = w_prev[i]; r[SB_WEST] = w_est[i]; r[SB_WY] = w_y[i]; r[SB_WZ] = w_z[i];
-      tv[i] = t[i];
-    }
-    const bool affine = in_scale && alpha && beta;
-    SG_REQUIRE(affine || (!in_scale && !alpha && !beta), "sb_sample: give all three score-wrapper arrays or none");
-    std::vector<float> cf;
-    if (affine) {
-      cf.assign((size_t)N * 4, 0.f);
-      for (int i = 0; i < N; ++i) { cf[4 * i] = in_scale[i]; cf[4 * i + 1] = alpha[i]; cf[4 * i + 2] = beta[i]; }
-    }
-    const unsigned long long* seed_dev = upload_tables(tab, tv, cf, seed, B);
-    compute_temb(tsteps_, N);
-    SG_CHECK(drt::memcpy_d2d(sy_, Y, n * 8, stream_));
+    }, in_scale, alpha, beta);
+    const FwdCtl& ctl = st.ctl;
     SG_CHECK(drt::memcpy_d2d(sx_, Y, n * 8, stream_));          // x_0 = y
     DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_, 0);
 
     SamplerArgs sa{};
-    sa.x = sx_; sa.x_mean = sxm_; sa.y = sy_; sa.score = sscore_; sa.noise = noise; sa.seed = seed_dev;
+    sa.x = sx_; sa.x_mean = sxm_; sa.y = sy_; sa.score = sscore_; sa.noise = noise; sa.seed = st.seed;
     sa.table = step_table_; sa.step_ptr = step_ctr_; sa.n = (int)n; sa.add_noise = stochastic ? 1 : 0; sa.B = B; sa.per = F * T;
     sa.draw_base = 0; sa.draw_per_step = 1;
     const dim3 eg((unsigned)((n + 255) / 256));
-    FwdCtl ctl{bias_table_, 0, tot_temb_, step_ctr_, tsteps_, 0, 1, -1.0f};
-    if (affine) { ctl.coef = coef_table_; ctl.coef_bstride = 0; ctl.coef_sstride = 1; }
     const long long FT = (long long)F * T;
     auto step_body = [&]() {
       arena_.reset();
@@ -551,22 +532,12 @@ class Engine {
       DRT_LAUNCH(sampler_sb_kernel, eg, dim3(256), stream_, sa);
       DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
     };
-    GraphKey key{B, F, T, 100 + stochastic, 0, 0, affine ? 2 : 0, nullptr, (const void*)noise, 0.f, 1};
-    if (use_graph && drt::graphs_supported()) {
-      if (!graph_valid_ || !(key == graph_key_)) {
-        invalidate_graph();
-        capture_step(step_body);
-        graph_key_ = key;
-      }
-      for (int i = 0; i < N; ++i) SG_CHECK(drt::graph_launch(&graph_, stream_));
-    } else {
-      for (int i = 0; i < N; ++i) step_body();
-    }
+    run_steps(N, GraphKey{B, F, T, 100 + stochastic, 0, 0, ctl.coef ? 2 : 0, nullptr, (const void*)noise, 0.f, 1}, use_graph, step_body);
     SG_CHECK(drt::memcpy_d2d(out, sx_, n * 8, stream_));
     nfe_ = N;
   }
   // the reference's fp32 expressions: g = sigma_min (sigma_max / sigma_min)^t sqrt(2 lambda); 0.5 g^2
-  static double ode_g2half(const OdeCfg& oc, float tf) {
+  static double ode_g2half(const sgmse_ode_cfg& oc, float tf) {
     const double lam = std::log((double)oc.sigma_max / (double)oc.sigma_min);
     const float g = (float)((double)oc.sigma_min * std::pow((double)oc.sigma_max / (double)oc.sigma_min, (double)tf) * std::sqrt(2.0 * lam));
     return (double)(g * g * 0.5f);
@@ -587,7 +558,7 @@ class Engine {
   // group), one table of [G][ODE_ROWS][ODE_STRIDE] doubles up, G error sums back.  coef_fn is called once per upload with its nt G
   // times STAGE-MAJOR (t[stage * G + g]): nt = 1 for f0 and for the probe of select_initial_step, 6 for a round.
   // Prior: x0 (given start state), else y + std1 z with z = noise (replayed, [B][F][T]) or the Philox stream of (seed, streams).
-  void ode_run(const float2* Y, float2* out, int B, int F, int T, const OdeCfg& oc, const float2* noise, const float2* x0,
+  void ode_run(const float2* Y, float2* out, int B, int F, int T, const sgmse_ode_cfg& oc, const float2* noise, const float2* x0,
                unsigned long long seed, bool per_utterance) {
     require_ready();
     const std::string who = per_utterance ? "ode_sample_each" : "ode_sample";
@@ -633,14 +604,8 @@ class Engine {
     const std::vector<float> one_row(SC_STRIDE, 0.f), one_t(1, (float)oc.t_end);
     const unsigned long long* seed_dev = upload_tables(one_row, one_t, std::vector<float>(), seed, B);    // (also consumes the noise-stream ids)
     SG_CHECK(drt::memcpy_d2d(sy_, Y, n * 8, stream_));
-    if (x0) {
-      SG_CHECK(drt::memcpy_d2d(sx_, x0, n * 8, stream_));
-    } else {
-      SamplerArgs sa{};
-      sa.x = sx_; sa.y = sy_; sa.noise = noise; sa.seed = seed_dev; sa.std1 = oc.std1; sa.n = (int)n; sa.B = B; sa.per = F * T;
-      sa.rag_off = ragged() ? rag_off_dev_[0] : nullptr;
-      DRT_LAUNCH(sampler_prior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), stream_, sa);
-    }
+    if (x0) SG_CHECK(drt::memcpy_d2d(sx_, x0, n * 8, stream_));
+    else draw_prior(noise, seed_dev, oc.std1, n, B, F * T);
 
     // time-embedding / time / wrapper rows: row = stage * G + group; the network's batch stride over them is 1 row when every
     // utterance is a group and 0 when the batch is one
@@ -680,20 +645,13 @@ class Engine {
           cf[4 * (size_t)r] = ga[r]; cf[4 * (size_t)r + 1] = al[r]; cf[4 * (size_t)r + 2] = be[r]; cf[4 * (size_t)r + 3] = 0.f;
         }
       }
-      if (hstage_pending_) { SG_CHECK(drt::event_sync(&hstage_ev_)); hstage_pending_ = false; }
       const size_t nb_tab = sizeof(double) * tab_doubles, nb_t = sizeof(float) * rows, nb_c = sizeof(float) * 4 * rows;
-      if (nb_tab + nb_t + nb_c > hstage_cap_) {
-        if (hstage_) drt::free_host(hstage_);
-        hstage_ = nullptr; hstage_cap_ = 0;
-        SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&hstage_), nb_tab + nb_t + nb_c));
-        hstage_cap_ = nb_tab + nb_t + nb_c;
-      }
-      memcpy(hstage_, table.data(), nb_tab); memcpy(hstage_ + nb_tab, tf.data(), nb_t); memcpy(hstage_ + nb_tab + nb_t, cf.data(), nb_c);
-      SG_CHECK(drt::memcpy_h2d(ode_table_, hstage_, nb_tab, stream_));
-      SG_CHECK(drt::memcpy_h2d(tsteps_, hstage_ + nb_tab, nb_t, stream_));
-      if (oc.coef_fn) SG_CHECK(drt::memcpy_h2d(coef_table_, hstage_ + nb_tab + nb_t, nb_c, stream_));
-      SG_CHECK(drt::event_record(&hstage_ev_, stream_));
-      hstage_pending_ = true;
+      char* hs = stage_.acquire(nb_tab + nb_t + nb_c);
+      memcpy(hs, table.data(), nb_tab); memcpy(hs + nb_tab, tf.data(), nb_t); memcpy(hs + nb_tab + nb_t, cf.data(), nb_c);
+      SG_CHECK(drt::memcpy_h2d(ode_table_, hs, nb_tab, stream_));
+      SG_CHECK(drt::memcpy_h2d(tsteps_, hs + nb_tab, nb_t, stream_));
+      if (oc.coef_fn) SG_CHECK(drt::memcpy_h2d(coef_table_, hs + nb_tab + nb_t, nb_c, stream_));
+      stage_.commit(stream_);
       compute_temb(tsteps_, rows);
       DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_, 0);
     };
@@ -2051,52 +2009,55 @@ class Engine {
     drop(h4);
   }
 
-  // what a captured step depends on.  The Philox seed is NOT part of it: the sampler kernels read it from a device word
-  // (upload_tables), so one capture serves every utterance / batch of a run (the Python samplers draw a fresh seed per call)
-  struct GraphKey {
-    int B, F, T, corr, ncorr, pred, pf; const void* y; const void* noise; float theta; int dps;
-    bool operator==(const GraphKey& o) const {
-      return B == o.B && F == o.F && T == o.T && corr == o.corr && ncorr == o.ncorr && pred == o.pred && pf == o.pf && y == o.y &&
-             noise == o.noise && theta == o.theta && dps == o.dps;
+  // ONE page-locked staging buffer is the host side of every table upload (upload_tables, the rounds of ode_run), so the copies are
+  // asynchronous and a sampler call never synchronises the host with the stream (no hidden host syncs): the caller may
+  // already enqueue the next batch's front end while this one samples.  acquire(n) returns n bytes of it once the event recorded
+  // behind the previous use's copies has passed (for a new call it has, long before: the copies are the first thing a call
+  // enqueues); commit(stream) records that event behind the copies just enqueued on `stream`.
+  struct HostStage {
+    char* hstage_ = nullptr; size_t cap_ = 0; drt::event_t ev_{}; bool ev_init_ = false, pending_ = false;
+    ~HostStage() { if (hstage_) drt::free_host(hstage_); if (ev_init_) drt::event_destroy(&ev_); }
+    char* acquire(size_t n) {
+      if (pending_) { SG_CHECK(drt::event_sync(&ev_)); pending_ = false; }
+      if (n > cap_) {
+        if (hstage_) drt::free_host(hstage_);
+        hstage_ = nullptr; cap_ = 0;
+        n = std::max(n, size_t(1) << 16);
+        SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&hstage_), n));
+        cap_ = n;
+      }
+      return hstage_;
     }
-  };
-  // Per-call sampler constants -> device: the step table, the time steps, the score-wrapper rows (may be empty) and the noise
-  // table -- seed word + one noise-stream id per utterance (SamplerArgs::seed; ids given by set_noise_streams are consumed by the
-  // next sampler call of the same batch size, otherwise utterance b gets stream b).  The host side of the copies is ONE page-locked
-  // staging buffer, so the copies are asynchronous and a sampler call never synchronises the host with the stream (no
-  // hidden host syncs): the caller may already enqueue the next batch's front end while this one samples.  The staging buffer is
-  // reused by the next call once the event recorded behind these copies has passed (it has, long before: the copies are the
-  // first thing a call enqueues).
+    void commit(drt::stream_t stream) {
+      if (!ev_init_) { SG_CHECK(drt::event_create(&ev_)); ev_init_ = true; }
+      SG_CHECK(drt::event_record(&ev_, stream));
+      pending_ = true;
+    }
+  } stage_;
+  // Per-call sampler constants -> device (through stage_): the step table, the time steps, the score-wrapper rows (may be empty) and
+  // the noise table -- seed word + one noise-stream id per utterance (SamplerArgs::seed; ids given by set_noise_streams are consumed
+  // by the next sampler call of the same batch size, otherwise utterance b gets stream b).
   const unsigned long long* upload_tables(const std::vector<float>& tab, const std::vector<float>& tv, const std::vector<float>& cf,
                                           unsigned long long seed, int B) {
     SG_REQUIRE(B + 1 <= kMaxStreams, "batch too large for the noise-stream table");
     if (!seed_dev_) seed_dev_ = static_cast<unsigned long long*>(dev_alloc((size_t)kMaxStreams * 8));
     const size_t nb_seed = ((size_t)B + 1) * 8, nb_tab = tab.size() * 4, nb_tv = tv.size() * 4, nb_cf = cf.size() * 4;
-    const size_t total = nb_seed + nb_tab + nb_tv + nb_cf;
-    if (hstage_pending_) { SG_CHECK(drt::event_sync(&hstage_ev_)); hstage_pending_ = false; }
-    if (total > hstage_cap_) {
-      if (hstage_) drt::free_host(hstage_);
-      hstage_cap_ = std::max(total, size_t(1) << 16);
-      SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&hstage_), hstage_cap_));
-    }
-    unsigned long long* hs = reinterpret_cast<unsigned long long*>(hstage_);
+    char* q = stage_.acquire(nb_seed + nb_tab + nb_tv + nb_cf);
+    unsigned long long* hs = reinterpret_cast<unsigned long long*>(q);
     hs[0] = seed;
     const bool given = (int)streams_next_.size() == B;
     for (int b = 0; b < B; ++b) hs[1 + b] = given ? streams_next_[b] : (unsigned long long)b;
     streams_next_.clear();
-    char* q = hstage_ + nb_seed;
+    q += nb_seed;
     memcpy(q, tab.data(), nb_tab); memcpy(q + nb_tab, tv.data(), nb_tv);
     if (nb_cf) memcpy(q + nb_tab + nb_tv, cf.data(), nb_cf);
     SG_CHECK(drt::memcpy_h2d(seed_dev_, hs, nb_seed, stream_));
     SG_CHECK(drt::memcpy_h2d(step_table_, q, nb_tab, stream_));
     SG_CHECK(drt::memcpy_h2d(tsteps_, q + nb_tab, nb_tv, stream_));
     if (nb_cf) SG_CHECK(drt::memcpy_h2d(coef_table_, q + nb_tab + nb_tv, nb_cf, stream_));
-    if (!hstage_ev_init_) { SG_CHECK(drt::event_create(&hstage_ev_)); hstage_ev_init_ = true; }
-    SG_CHECK(drt::event_record(&hstage_ev_, stream_));
-    hstage_pending_ = true;
+    stage_.commit(stream_);
     return seed_dev_;
   }
-  char* hstage_ = nullptr; size_t hstage_cap_ = 0; drt::event_t hstage_ev_{}; bool hstage_ev_init_ = false, hstage_pending_ = false;
   static constexpr int kMaxStreams = 4096;
   std::vector<unsigned long long> streams_next_;
   unsigned long long* seed_dev_ = nullptr;

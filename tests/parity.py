@@ -1038,6 +1038,39 @@ def check_graph_update_path(dev, name="fwd_nf32"):
         assert cur[0] + cur[1] == prev[0] + prev[1] + 1, hist                    # every new composition re-captures: update or new instance
 
 
+def check_alternating_samplers_share_one_graph_slot(dev):
+    """pc_sample and sb_sample alternate on ONE context with use_graph=True.  Both replay the engine's single captured step, and
+    their launch sequences differ, so a stale step of the one sampler cannot be updated in place into a step of the other: every
+    call has to end with a step of its own in the slot.  Each result must equal, bit for bit, the same call run eagerly on a
+    fresh context (which captures nothing).  Returns graph_captures() + graph_updates() of the shared context after each of the
+    four calls, counted from its value before the first (all zero where graphs are unsupported and the eager path runs)."""
+    from sgmse_amd.sdes import SBVESDE
+    cfg = NO.NetCfg.for_variant("ncsnpp", nf=32)
+    N = 3
+    y = synth.synth_spec(2, 256, 64, seed=3).to(dev)
+    sb_table = SBVESDE(2.6, 0.4, N=N).sb_step_table(1e-4, "sde", N)
+
+    def samplers():          # (context, its pc call, its sb call) of a new model: in-kernel noise, fixed seed
+        m, _ = make_model(cfg, dev)
+        ctx = m.dnn.engine(torch.device(dev))
+        table, std1 = m.sde.step_table(0.03, 0.5, N), float(m.sde._std(torch.ones(1))[0])
+        pc = lambda g: ctx.pc_sample(y, table, theta=float(m.sde.theta), std1=std1, corrector="ald", corrector_steps=1,
+                                     predictor="reverse_diffusion", probability_flow=False, denoise=True, noise=None, seed=5,
+                                     use_graph=g, snr=0.5)[0]
+        sb = lambda g: ctx.sb_sample(y, sb_table, stochastic=True, noise=None, seed=5, use_graph=g)[0]
+        return ctx, pc, sb
+
+    eager = {"pc": samplers()[1](False), "sb": samplers()[2](False)}
+    assert all(torch.isfinite(torch.view_as_real(v)).all() for v in eager.values()) and not torch.equal(eager["pc"], eager["sb"])
+    ctx, pc, sb = samplers()
+    base, hist = ctx.graph_captures() + ctx.graph_updates(), []
+    for i, (name, call) in enumerate((("pc", pc), ("sb", sb), ("pc", pc), ("sb", sb))):
+        out = call(True)
+        hist.append(ctx.graph_captures() + ctx.graph_updates() - base)
+        assert torch.equal(out, eager[name]), (i, name)
+    return hist
+
+
 def check_ragged_variants(dev):
     """Ragged batches through the other two network variants: ncsnpp_v2 with the new-code score wrapper (the exit kernel reads
     x_t of the packed sampler state) and ncsnpp_48k (no pyramids, final convolution), on a 64-bin network."""

@@ -242,6 +242,10 @@ def test_pc_sampler_matches_reference(emu):
     P.check_sampler_golden(emu, "pc_N4", batch=1)
 
 
+def test_alternating_samplers_share_one_graph_slot(emu):
+    assert P.check_alternating_samplers_share_one_graph_slot(emu) == [0, 0, 0, 0]      # no graphs on the emulator: the eager path
+
+
 def test_pc_sampler_with_two_corrector_steps_matches_reference(emu):
     P.check_sampler_golden(emu, "pc_N4_c2", batch=1)
 

@@ -250,6 +250,12 @@ def test_sampler_graph_equals_eager(hip):
     assert torch.equal(a, c)        # replay of the cached graph
 
 
+def test_alternating_samplers_share_one_graph_slot(hip):
+    """pc, sb, pc, sb on one context: each call brings the one captured step up to date exactly once (a capture or an in-place
+    update) and gives the bits of its eager run on a fresh context."""
+    assert P.check_alternating_samplers_share_one_graph_slot(hip) == [1, 2, 3, 4]
+
+
 def test_python_loop_fallback_matches_native(hip):
     """Registry predictors/correctors without a fused kernel run the reference-style Python loop over the HIP network;
     with the natively supported pair both paths must agree (different noise source -> compare with replay disabled:
