@@ -43,9 +43,17 @@ __device__ __forceinline__ uint32_t drt_f32x2_to_f16x2(float x0, float x1) {
 __device__ __forceinline__ float drt_sub_f16_lo(float x, uint32_t h) { float r; asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x)); return r; }
 __device__ __forceinline__ float drt_sub_f16_hi(float x, uint32_t h) { float r; asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(x)); return r; }
 // IEEE single multiply / add that the compiler must not contract into a fused multiply-add (where a reference's rounding
-// sequence has to be reproduced operation by operation)
-__device__ __forceinline__ float drt_mul_rn(float a, float b) { return __fmul_rn(a, b); }
-__device__ __forceinline__ float drt_add_rn(float a, float b) { return __fadd_rn(a, b); }
+// sequence has to be reproduced operation by operation).  NOT __fmul_rn / __fadd_rn: the HIP headers define them as plain a * b and
+// a + b, which the default -ffp-contract=fast-honor-pragmas fuses after inlining (the sampler_sb_kernel sum compiled to v_mul +
+// 2 v_fmac); with contraction switched off in the function the operations carry no `contract` flag and stay v_mul_f32 / v_add_f32
+__device__ __forceinline__ float drt_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float drt_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
 __device__ __forceinline__ float drt_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32
 // Raw buffer view of a global fp32 tensor slice: address = base + voff (per-lane VGPR, bytes) + soff (uniform SGPR, bytes).
 // One buffer_load/store_dword per access with NO address arithmetic on the vector ALU; offsets must stay below 2^31.
