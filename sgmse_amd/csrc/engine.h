@@ -15,6 +15,7 @@
 
 #include <deque>
 #include <sgmse_devrt.h>
+#include "dev_memory.h"
 #include "kernels_conv.h"
 #include "conv_launch.h"
 #include "kernels_norm_fir.h"
@@ -25,11 +26,6 @@
 #include "../../include/sgmse_hip.h"     // sgmse_sampler_cfg, sgmse_ode_cfg: the samplers take the public structs
 
 namespace sgmse {
-
-struct EngineError : std::runtime_error { using std::runtime_error::runtime_error; };
-
-#define SG_CHECK(expr) do { int _e = (expr); if (_e != 0) { char _b[256]; snprintf(_b, sizeof _b, "%s failed: %s (%d)", #expr, drt::error_string(_e), _e); throw EngineError(_b); } } while (0)
-#define SG_REQUIRE(cond, msg) do { if (!(cond)) throw EngineError(std::string(msg)); } while (0)
 
 struct NetCfg {
   int variant = 0;            // 0: ncsnpp, 1: ncsnpp_48k
@@ -310,14 +306,9 @@ class Engine {
     stream_ = reinterpret_cast<drt::stream_t>(stream);
     read_knobs();
   }
-  ~Engine() {
-    for (void* p : owned_) drt::free_dev(p);
-    for (void* p : wowned_) drt::free_dev(p);
+  ~Engine() {      // (buffers and events: released by their holders)
     if (graph_valid_ || graph_stale_) drt::graph_destroy(&graph_);
-    if (ode_host_) drt::free_host(ode_host_);
-    for (drt::event_t& e : side_ev_) drt::event_destroy(&e);
     if (side_stream_ready_) drt::stream_destroy(side_stream_);
-    for (ProfRec& r : prof_recs_) { drt::event_destroy(&r.a); drt::event_destroy(&r.b); }
   }
 
   drt::stream_t stream() const { return stream_; }
@@ -330,13 +321,12 @@ class Engine {
   void load_weights(const char* const* names, const void* const* ptrs, const long long* numels, int n, int on_device) {
     invalidate_graph();            // a captured graph refers to the old weight buffers
     weights_ready_ = false;
-    free_weight_allocs();
+    release_weights();
     auto manifest = param_manifest(cfg_);
     std::map<std::string, size_t> want;
     size_t total = 0;
     for (auto& kv : manifest) { want[kv.first] = kv.second; total += (kv.second + 63) / 64 * 64; }
-    float* blob = static_cast<float*>(dev_alloc_w(total * 4));
-    blob_ = blob; blob_elems_ = total;
+    float* blob = keep(fresh(total * 4));
     std::map<std::string, std::pair<const void*, long long>> given;
     for (int i = 0; i < n; ++i) given[names[i]] = {ptrs[i], numels[i]};
     size_t off = 0;
@@ -438,7 +428,7 @@ class Engine {
   void draw_prior(const float2* noise, const unsigned long long* seed_dev, float std1, size_t n, int B, int per) {
     SamplerArgs sa{};
     sa.x = sx_; sa.y = sy_; sa.noise = noise; sa.seed = seed_dev; sa.std1 = std1; sa.n = (int)n; sa.B = B; sa.per = per;
-    sa.rag_off = ragged() ? rag_off_dev_[0] : nullptr;
+    sa.rag_off = rag_off0();
     DRT_LAUNCH(sampler_prior_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), stream_, sa);
   }
 
@@ -450,7 +440,7 @@ class Engine {
     ensure_shape(B, F, T, sc.N);
     SG_REQUIRE(!ragged() || sc.corrector != 2, "ragged batches: the Langevin corrector couples the utterances of a batch (correctors.py:50-52) and is not supported");
     SG_REQUIRE(!ragged() || !noise, "ragged batches: replayed noise is not supported (in-kernel noise only)");
-    const size_t n = ragged() ? rag_pix_[0] : (size_t)B * F * T;     // complex elements of Y / the result, utterance after utterance
+    const size_t n = ragged() ? rag_[0].pix : (size_t)B * F * T;     // complex elements of Y / the result, utterance after utterance
     const StepSetup st = begin_steps("pc_sample", Y, n, B, sc.N, seed, [&](int i, float* r) {
       r[SC_T] = sc.t[i]; r[SC_DT] = sc.dt[i]; r[SC_G] = sc.G[i]; r[SC_G2] = sc.G2[i];
       if (sc.corrector == 1) { r[SC_ALD_EPS] = sc.ald_eps[i]; r[SC_ALD_NOISE] = sc.ald_noise[i]; }
@@ -466,12 +456,12 @@ class Engine {
     sa.table = step_table_; sa.step_ptr = step_ctr_; sa.theta = sc.theta; sa.std1 = sc.std1; sa.n = (int)n;
     sa.score_w = sc.probability_flow ? 0.5f : 1.0f;
     sa.snr = sc.snr; sa.B = B; sa.per = F * T; sa.partial = lang_partial_; sa.lang = lang_scal_;
-    sa.rag_off = ragged() ? rag_off_dev_[0] : nullptr;
+    sa.rag_off = rag_off0();
     const dim3 eg((unsigned)((n + 255) / 256));
 
     draw_prior(noise, st.seed, sc.std1, n, B, F * T);
     SG_CHECK(drt::memcpy_d2d(sxm_, sx_, n * 8, stream_));
-    DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_, 0);
+    DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_.get(), 0);
 
     const long long FT = ragged() ? 1 : (long long)F * T;          // batch stride of x / y (ragged: multiplier of the utterance's offset)
     auto step_body = [&]() {
@@ -495,7 +485,7 @@ class Engine {
       }
       // NonePredictor.update_fn returns (x, x) (predictors.py:69-76): xt_mean := xt also after a corrector moved them apart
       if (sc.predictor == 0 && ncorr > 0) SG_CHECK(drt::memcpy_d2d(sxm_, sx_, n * 8, stream_));
-      DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
+      DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_.get());
     };
     run_steps(sc.N, GraphKey{B, F, T, sc.corrector, ncorr, sc.predictor, sc.probability_flow + (ctl.coef ? 2 : 0), (const void*)sy_, (const void*)noise,
                              sc.theta + 1000.f * sc.snr * (sc.corrector == 2), draws_per_step},      // (set_frames invalidates the graph itself)
@@ -518,7 +508,7 @@ class Engine {
     }, in_scale, alpha, beta);
     const FwdCtl& ctl = st.ctl;
     SG_CHECK(drt::memcpy_d2d(sx_, Y, n * 8, stream_));          // x_0 = y
-    DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_, 0);
+    DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_.get(), 0);
 
     SamplerArgs sa{};
     sa.x = sx_; sa.x_mean = sxm_; sa.y = sy_; sa.score = sscore_; sa.noise = noise; sa.seed = st.seed;
@@ -530,7 +520,7 @@ class Engine {
       arena_.reset();
       run_forward(sx_, FT, sy_, FT, sscore_, B, F, T, ctl);
       DRT_LAUNCH(sampler_sb_kernel, eg, dim3(256), stream_, sa);
-      DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
+      DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_.get());
     };
     run_steps(N, GraphKey{B, F, T, 100 + stochastic, 0, 0, ctl.coef ? 2 : 0, nullptr, (const void*)noise, 0.f, 1}, use_graph, step_body);
     SG_CHECK(drt::memcpy_d2d(out, sx_, n * 8, stream_));
@@ -571,25 +561,14 @@ class Engine {
     SG_REQUIRE(!per_utterance || B <= kOdeEachMaxB, "ode_sample_each: batch too large");
     const int G = per_utterance ? B : 1;
     ensure_shape(B, F, T, ODE_ROWS * G);
-    const size_t n = ragged() ? rag_pix_[0] : (size_t)B * F * T;     // complex elements, utterance after utterance
+    const size_t n = ragged() ? rag_[0].pix : (size_t)B * F * T;     // complex elements, utterance after utterance
     const size_t per = per_utterance ? (size_t)F * T : n;            // ... of a group (ragged: of the longest)
-    if (n > ode_n_) {
-      for (float2** q : {&ode_k_[0], &ode_k_[1], &ode_k_[2], &ode_k_[3], &ode_k_[4], &ode_k_[5], &ode_k_[6], &ode_xs_}) {
-        if (*q) dev_free_owned(*q);
-        *q = static_cast<float2*>(dev_alloc(n * 8));
-      }
-      ode_n_ = n;
-    }
-    if (G > ode_cap_) {
-      for (double** q : {&ode_table_, &ode_partial_, &ode_result_}) if (*q) dev_free_owned(*q);
-      if (ode_host_) drt::free_host(ode_host_);
-      ode_table_ = static_cast<double*>(dev_alloc(sizeof(double) * G * ODE_ROWS * ODE_STRIDE));
-      ode_partial_ = static_cast<double*>(dev_alloc(sizeof(double) * G * ODE_NBLK * ODE_NSUM));
-      ode_result_ = static_cast<double*>(dev_alloc(sizeof(double) * G * ODE_NSUM));
-      ode_host_ = nullptr;
-      SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&ode_host_), sizeof(double) * G * ODE_NSUM));
-      ode_cap_ = G;
-    }
+    for (DevArray<float2>& k : ode_k_) grow(k, n * 8);
+    grow(ode_xs_, n * 8);
+    grow(ode_table_, sizeof(double) * G * ODE_ROWS * ODE_STRIDE);
+    grow(ode_partial_, sizeof(double) * G * ODE_NBLK * ODE_NSUM);
+    grow(ode_result_, sizeof(double) * G * ODE_NSUM);
+    ode_host_.ensure(sizeof(double) * G * ODE_NSUM);
     ode_ctl_.assign(G, OdeControl());
     ode_rounds_ = ode_wasted_ = 0; nfe_ = 0;
     std::vector<OdeControl>& cs = ode_ctl_;
@@ -618,12 +597,12 @@ class Engine {
     auto base_args = [&]() {
       OdeEachArgs e{};
       OdeArgs& a = e.a;
-      a.y = (const float*)sy_; a.score = (const float*)sscore_;
-      for (int j = 1; j < 6; ++j) a.k[j] = (const float*)ode_k_[j];
+      a.y = (const float*)sy_.get(); a.score = (const float*)sscore_.get();
+      for (int j = 1; j < 6; ++j) a.k[j] = (const float*)ode_k_[j].get();
       a.table = ode_table_; a.step_ptr = step_ctr_; a.row = -1; a.theta = oc.theta;
       a.atol = oc.atol; a.rtol = oc.rtol; a.partial = ode_partial_; a.result = ode_result_;
-      e.xbuf[0] = (float*)sx_; e.xbuf[1] = (float*)sxm_; e.kbuf[0] = (float*)ode_k_[0]; e.kbuf[1] = (float*)ode_k_[6];
-      e.rag_off = ragged() ? rag_off_dev_[0] : nullptr; e.per = (long long)per; e.kout_sel = -1;
+      e.xbuf[0] = (float*)sx_.get(); e.xbuf[1] = (float*)sxm_.get(); e.kbuf[0] = (float*)ode_k_[0].get(); e.kbuf[1] = (float*)ode_k_[6].get();
+      e.rag_off = rag_off0(); e.per = (long long)per; e.kout_sel = -1;
       return e;
     };
     const size_t tab_doubles = (size_t)G * ODE_ROWS * ODE_STRIDE;
@@ -653,7 +632,7 @@ class Engine {
       if (oc.coef_fn) SG_CHECK(drt::memcpy_h2d(coef_table_, hs + nb_tab + nb_t, nb_c, stream_));
       stage_.commit(stream_);
       compute_temb(tsteps_, rows);
-      DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_, 0);
+      DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_.get(), 0);
     };
     auto evaluate = [&](const float2* at) {      // one batch evaluation at the step counter's time rows
       arena_.reset();
@@ -661,7 +640,7 @@ class Engine {
       ++nfe_;
     };
     auto read_sums = [&]() {                     // second stage of a reduction + the one transfer of a round: G x ODE_NSUM doubles
-      DRT_LAUNCH(ode_reduce_final_each_kernel, dim3(G), dim3(64), stream_, (const double*)ode_table_, (const double*)ode_partial_, ode_result_);
+      DRT_LAUNCH(ode_reduce_final_each_kernel, dim3(G), dim3(64), stream_, (const double*)ode_table_, (const double*)ode_partial_, ode_result_.get());
       SG_CHECK(drt::memcpy_d2h(ode_host_, ode_result_, sizeof(double) * G * ODE_NSUM, stream_));
       SG_CHECK(drt::stream_sync(stream_));
       check_launch();
@@ -696,9 +675,9 @@ class Engine {
         times[g] = cs[g].t + h0 * cs[g].dir;
       }
       upload(1, active);
-      { OdeEachArgs e = base_args(); e.a.row = 6; e.a.nterms = 1; e.a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
+      { OdeEachArgs e = base_args(); e.a.row = 6; e.a.nterms = 1; e.a.xnext = (float*)ode_xs_.get(); DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
       evaluate(ode_xs_);
-      { OdeEachArgs e = base_args(); e.a.xs = (const float*)ode_xs_; e.kout_sel = 6; e.a.self = 6; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
+      { OdeEachArgs e = base_args(); e.a.xs = (const float*)ode_xs_.get(); e.kout_sel = 6; e.a.self = 6; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
       { OdeEachArgs e = base_args(); e.d2 = 1; DRT_LAUNCH(ode_init_norms_each_kernel, rgrid, dim3(256), stream_, e); }
       read_sums();
       for (int g = 0; g < G; ++g) cs[g].first_step_from_probe(ode_host_[g * ODE_NSUM + 1]);
@@ -721,15 +700,15 @@ class Engine {
       }
       ++ode_rounds_; ode_wasted_ += 6 * (G - nactive);
       upload(6, active);
-      { OdeEachArgs e = base_args(); e.a.row = 6; e.a.nterms = 1; e.a.xnext = (float*)ode_xs_; DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
+      { OdeEachArgs e = base_args(); e.a.row = 6; e.a.nterms = 1; e.a.xnext = (float*)ode_xs_.get(); DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e); }
       for (int st = 0; st < 5; ++st) {
         evaluate(ode_xs_);
         OdeEachArgs e = base_args();
-        e.a.xs = (const float*)ode_xs_; e.a.kout = (float*)ode_k_[st + 1]; e.a.self = st + 1; e.a.nterms = st + 2;
-        e.a.xnext = (float*)ode_xs_;              // (in place: each thread reads its elements before it writes them)
+        e.a.xs = (const float*)ode_xs_.get(); e.a.kout = (float*)ode_k_[st + 1].get(); e.a.self = st + 1; e.a.nterms = st + 2;
+        e.a.xnext = (float*)ode_xs_.get();              // (in place: each thread reads its elements before it writes them)
         e.to_new_state = st == 4 ? 1 : 0;         // y_new: to the stage-input buffer for the network AND to the group's other state buffer
         DRT_LAUNCH(ode_stage_each_kernel, sgrid, dim3(256), stream_, e);
-        DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_);
+        DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_.get());
       }
       evaluate(ode_xs_);
       { OdeEachArgs e = base_args(); DRT_LAUNCH(ode_error_each_kernel, rgrid, dim3(256), stream_, e); }
@@ -762,13 +741,14 @@ class Engine {
   int graph_updates() const { return graph_updates_; }       // ... captured and applied to the existing executable in place
   int split_mode() const { return split_mode_; }
   bool winograd() const { return split_mode_ == 2 && wino_; }
-  size_t arena_bytes() const { return arena_cap_; }
+  size_t arena_bytes() const { return arena_buf_.capacity(); }
 
   // ---- single ops (op-level C ABI + tests) ------------------------------------------------------------------
   // per-utterance max |x| of one or two NCHW tensors -> [B] (+ [B]) floats, for the op-level entry points
-  float* input_bounds(const float* x1, int C1, const float* x2, int C2, int B, int HW) {
+  DevBuf input_bounds(const float* x1, int C1, const float* x2, int C2, int B, int HW) {
     const size_t per = (size_t)B * kAmaxSpread;
-    float* out = static_cast<float*>(dev_alloc_tmp(2 * per * 4));
+    DevBuf buf = fresh(2 * per * 4);
+    float* out = buf.as<float>();
     SG_CHECK(drt::memset_dev(out, 0, 2 * per * 4, stream_));
     for (int b = 0; b < B; ++b) {
       const size_t n1 = (size_t)C1 * HW;
@@ -780,14 +760,54 @@ class Engine {
                    out + per + (size_t)b * kAmaxSpread);
       }
     }
-    return out;
+    return buf;
   }
 
   // the bound gn_finalize_kernel leaves for an fp16x2 3x3 consumer, for a producer given as explicit coefficients (or none)
-  float* producer_bound(const float* in_scale, const float* in_shift, int C, const float* amax1, const float* amax2, int B) {
-    float* out = static_cast<float*>(dev_alloc_tmp((size_t)B * kAmaxSpread * 4));
+  DevBuf producer_bound(const float* in_scale, const float* in_shift, int C, const float* amax1, const float* amax2, int B) {
+    DevBuf buf = fresh((size_t)B * kAmaxSpread * 4);
+    float* out = buf.as<float>();
     DRT_LAUNCH(xform_bound_kernel, dim3(B), dim3(64), stream_, in_scale, in_shift, C, amax1, amax2, out);
-    return out;
+    return buf;
+  }
+
+  // ---- stand-alone convolution launches (op_conv2d, bench_conv): what Engine::conv() takes from the layer and from the forward,
+  // made on the spot from OIHW weights and the input tensors
+  struct ConvPack { enum Kind { Mfma, Thin, Split, Wino } kind; int smode = 0; WinoForm form = WinoForm::F23; int co_t = 0; };
+  // the launch arguments and the scratch behind their pointers.  Declare it in front of the launch: its scope then ends behind the
+  // stream synchronisation that follows the launch.  (When an exception unwinds it earlier the buffers are freed with work still
+  // queued; that is sound, freeing device memory waits for the device.  The same holds for every scoped DevBuf of this file.)
+  struct StandaloneConv { ConvArgs a{}; DevBuf packed, bounds, xbound; };
+  // a0: sources, shape and fused producer.  Packs the weights for the family; for the fp16x2 families (dynamic input scale) also
+  // computes the range bounds as the producers of the forward would have left them.
+  StandaloneConv standalone_conv(const ConvArgs& a0, const ConvPack& f, const float* w_oihw, int ks) {
+    StandaloneConv s;
+    ConvArgs& a = s.a = a0;
+    const int Cin = a.C1 + a.C2;
+    switch (f.kind) {
+      case ConvPack::Mfma: s.packed = pack_mfma(oihw_sources(w_oihw, ks, Cin, a.Cout), f.co_t); break;
+      case ConvPack::Thin: s.packed = pack_thin(w_oihw, Cin, a.Cout); break;
+      case ConvPack::Split: s.packed = pack_split(w_oihw, ks, Cin, a.Cout, f.smode, &a.co_scale); break;
+      case ConvPack::Wino: s.packed = pack_wino(f.form, w_oihw, Cin, a.Cout, &a.co_scale); break;      // (all Winograd forms are fp16x2)
+    }
+    a.w = s.packed.as<float>();
+    if (f.kind == ConvPack::Wino || (f.kind == ConvPack::Split && f.smode == 2)) {
+      s.bounds = input_bounds(a.src1, a.C1, a.src2, a.C2, a.B, a.H * a.W);
+      const float* am1 = s.bounds.as<float>();
+      const float* am2 = a.src2 ? am1 + (size_t)a.B * kAmaxSpread : nullptr;
+      if (ks == 1 && a.in_scale == nullptr) bind_bounds(a, 1, nullptr, am1, am2);      // raw input, as the network's shortcuts run it
+      else {      // a fused producer: the kernel scales by the bound of the producer's output (1x1: in the place of the raw range)
+        s.xbound = producer_bound(a.in_scale, a.in_shift, Cin, am1, am2, a.B);
+        bind_bounds(a, ks, s.xbound.as<float>(), s.xbound.as<float>(), nullptr);
+      }
+    }
+    return s;
+  }
+  // where an fp16x2 launch reads its input range: a 3x3 kernel from the bound of its (fused producer's) input, a 1x1 kernel from the
+  // range bounds of its sources
+  static void bind_bounds(ConvArgs& ca, int ks, const float* xbound, const float* amax1, const float* amax2) {
+    if (ks == 3) ca.xbound = xbound;
+    else { ca.amax1 = amax1; ca.amax2 = amax2; }
   }
 
   // the `force_direct` argument of sgmse_op_conv2d (include/sgmse_hip.h); sgmse_amd/ops.py maps its force_split names to these values
@@ -801,43 +821,26 @@ class Engine {
     a.Cout = Cout; a.B = B; a.H = H; a.W = W; a.in_scale = in_scale; a.in_shift = in_shift; a.in_act = in_act;
     ConvPlan pl = choose_conv_plan(ks, Cin, Cout, H, W);
     const bool wino = force_direct == FC_WINO || force_direct == FC_WINO_4ROW || force_direct == FC_WINO2D || force_direct == FC_WINO43 || force_direct == FC_WINO43_4ROW;
+    StandaloneConv s;      // (of whichever launch follows; released at the end of the function, behind the synchronisations)
     if (force_direct == FC_THIN) {                         // exact-fp32 VALU kernel of the C -> 4 pyramid convolutions
       SG_REQUIRE(conv_thin_eligible(ks, a.C1, C2, Cout), "op_conv2d: shape is not eligible for the thin-output kernel");
-      const float* pk = pack_thin(w_oihw, Cin, Cout, false);
-      a.w = pk;
-      launch_conv_thin(a, stream_);
+      s = standalone_conv(a, ConvPack{ConvPack::Thin}, w_oihw, ks);
+      launch_conv_thin(s.a, stream_);
       SG_CHECK(drt::stream_sync(stream_));
-      free_tmp(const_cast<float*>(pk));
     } else if (wino || force_direct == FC_SPLIT_B3 || force_direct == FC_SPLIT_H2) {      // the Winograd x fp16x2 forms and the split kernels
       const WinoForm form = force_direct == FC_WINO2D ? WinoForm::F2x2 : force_direct >= FC_WINO43 ? WinoForm::F43 : WinoForm::F23;
       const int smode = wino ? 2 : force_direct - 1;       // (all Winograd forms are fp16x2)
       if (!wino) SG_REQUIRE(conv_split_eligible(ks, a.C1, C2, Cout) || conv_thin_split_eligible(ks, a.C1, C2, Cout), "op_conv2d: shape is not eligible for the split kernels");
       else if (form == WinoForm::F43) SG_REQUIRE(ks == 3 && conv_wino43_eligible(a.C1, C2, Cout, W) && conv_wino43_aligned(a), "op_conv2d: shape is not eligible for the Winograd F(4,3) kernel");
       else SG_REQUIRE(ks == 3 && conv_wino_eligible(a.C1, C2, Cout, W), form == WinoForm::F2x2 ? "op_conv2d: shape is not eligible for the 2-D Winograd kernel" : "op_conv2d: shape is not eligible for the Winograd kernel");
-      const float* pk = wino ? pack_wino(form, w_oihw, Cin, Cout, false, &a.co_scale) : pack_split(w_oihw, ks, Cin, Cout, smode, false, &a.co_scale);
-      a.w = pk;
-      float *bounds = nullptr, *xb = nullptr;
-      if (smode == 2) {      // dynamic input scale: range bounds as the producers would have left them
-        bounds = input_bounds(x, a.C1, x2, C2, B, H * W);
-        const float* am2 = x2 ? bounds + (size_t)B * kAmaxSpread : nullptr;
-        if (ks == 1 && in_scale == nullptr) { a.amax1 = bounds; a.amax2 = am2; }      // raw input, as the network's shortcuts run it
-        else {      // a fused producer: the kernel scales by the bound of the producer's output (1x1: in the place of the raw range)
-          xb = producer_bound(in_scale, in_shift, Cin, bounds, am2, B);
-          if (ks == 1) a.amax1 = xb; else a.xbound = xb;
-        }
-      }
-      if (wino) launch_conv_wino(form, a, stream_, force_direct == FC_WINO_4ROW || force_direct == FC_WINO43_4ROW);
-      else launch_conv_split(a, ks, smode, stream_);
+      s = standalone_conv(a, wino ? ConvPack{ConvPack::Wino, smode, form} : ConvPack{ConvPack::Split, smode}, w_oihw, ks);
+      if (wino) launch_conv_wino(form, s.a, stream_, force_direct == FC_WINO_4ROW || force_direct == FC_WINO43_4ROW);
+      else launch_conv_split(s.a, ks, smode, stream_);
       SG_CHECK(drt::stream_sync(stream_));
-      free_tmp(const_cast<float*>(pk));
-      if (bounds) free_tmp(bounds);
-      if (xb) free_tmp(xb);
     } else if (pl.mfma && !force_direct && (C2 == 0 || a.C1 % ((ks == 3) ? 8 : 32) == 0)) {
-      const float* pk = pack_mfma(oihw_sources(w_oihw, ks, Cin, Cout), pl.co_t, false);
-      a.w = pk;
-      launch_conv_mfma(a, ks, pl, stream_);
+      s = standalone_conv(a, ConvPack{ConvPack::Mfma, 0, WinoForm::F23, pl.co_t}, w_oihw, ks);
+      launch_conv_mfma(s.a, ks, pl, stream_);
       SG_CHECK(drt::stream_sync(stream_));
-      free_tmp(const_cast<float*>(pk));
     } else {
       a.w = w_oihw;
       launch_conv_direct(a, ks, stream_);
@@ -848,9 +851,8 @@ class Engine {
   void op_groupnorm(const float* x, const float* gamma, const float* beta, float* out, int B, int C, int H, int W, int act,
                     const float* x2, int C2) {
     const int HW = H * W, C1 = C - C2;
-    float* stats = static_cast<float*>(dev_alloc_tmp((size_t)B * C * 2 * 4));
-    float* sc = static_cast<float*>(dev_alloc_tmp((size_t)B * C * 4));
-    float* sh = static_cast<float*>(dev_alloc_tmp((size_t)B * C * 4));
+    const DevBuf stats_buf = fresh((size_t)B * C * 2 * 4), sc_buf = fresh((size_t)B * C * 4), sh_buf = fresh((size_t)B * C * 4);
+    float *stats = stats_buf.as<float>(), *sc = sc_buf.as<float>(), *sh = sh_buf.as<float>();
     float* stats2 = stats + (size_t)B * C1 * 2;
     DRT_LAUNCH(gn_chan_stats_kernel, dim3(B * C1), dim3(256), stream_, x, (const float*)nullptr, C1, 0, HW, stats, Rag{nullptr, nullptr, nullptr}, 0);
     if (C2) DRT_LAUNCH(gn_chan_stats_kernel, dim3(B * C2), dim3(256), stream_, x2, (const float*)nullptr, C2, 0, HW, stats2, Rag{nullptr, nullptr, nullptr}, 0);
@@ -861,7 +863,6 @@ class Engine {
                (const float*)sh, act, out);
     SG_CHECK(drt::stream_sync(stream_));
     check_launch();
-    free_tmp(stats); free_tmp(sc); free_tmp(sh);
   }
 
   void op_fir(const float* x, float* out, int BC, int H, int W, int up, const float* in_scale, const float* in_shift, int in_act,
@@ -941,40 +942,27 @@ class Engine {
     SG_REQUIRE(!wino43 || conv_wino43_eligible(Cin, 0, Cout, W), "bench_conv: shape is not eligible for the Winograd F(4,3) kernel");
     const WinoForm wform = wino2d ? WinoForm::F2x2 : wino43 ? WinoForm::F43 : WinoForm::F23;
     const size_t nx = (size_t)B * Cin * H * W, no = (size_t)B * Cout * H * W, nw = (size_t)Cout * Cin * ks * ks;
-    float* x = static_cast<float*>(dev_alloc_tmp(nx * 4));
-    float* o = static_cast<float*>(dev_alloc_tmp(no * 4));
-    float* r = static_cast<float*>(dev_alloc_tmp(no * 4));
-    float* w = static_cast<float*>(dev_alloc_tmp(nw * 4));
-    float* sc = static_cast<float*>(dev_alloc_tmp((size_t)B * Cin * 8));
+    const DevBuf x_buf = fresh(nx * 4), o_buf = fresh(no * 4), r_buf = fresh(no * 4), w_buf = fresh(nw * 4), sc_buf = fresh((size_t)B * Cin * 8);
+    float *x = x_buf.as<float>(), *o = o_buf.as<float>(), *r = r_buf.as<float>(), *w = w_buf.as<float>(), *sc = sc_buf.as<float>();
     auto fill = [&](float* d, size_t n, uint32_t seed) {
       DRT_LAUNCH(fill_random_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), stream_, d, n, seed);
     };
     fill(x, nx, 1); fill(r, no, 2); fill(w, nw, 3); fill(sc, (size_t)B * Cin * 2, 4);
-    float* pk = const_cast<float*>(pack_mfma(oihw_sources(w, ks, Cin, Cout), pl.co_t, false));
-    ConvArgs a{};
-    a.src1 = x; a.C1 = Cin; a.w = pk; a.out = o; a.Cout = Cout; a.B = B; a.H = H; a.W = W; a.out_scale = 1.f;
-    a.ablate = ablate;
-    if (fused) { a.in_scale = sc; a.in_shift = sc + (size_t)B * Cin; a.in_act = 1; a.res = r; a.bias = w; a.out_scale = 0.70710678f; }
-    drt::event_t e0{}, e1{};
-    drt::event_create(&e0); drt::event_create(&e1);
-    const float* pk3 = nullptr;
-    float *bounds = nullptr, *xbound = nullptr;
-    if (b3 || wino || wino2d) {
-      pk3 = b3 ? pack_split(w, ks, Cin, Cout, smode, false, &a.co_scale) : pack_wino(wform, w, Cin, Cout, false, &a.co_scale); a.w = pk3;
-      if (!b3 || smode == 2) {
-        bounds = input_bounds(x, Cin, nullptr, 0, B, H * W);
-        if (ks == 1) {
-          a.in_scale = nullptr; a.in_shift = nullptr; a.in_act = 0;     // raw input, as in the network's shortcut layers
-          a.amax1 = bounds;
-        } else {
-          xbound = producer_bound(a.in_scale, a.in_shift, Cin, bounds, nullptr, B); a.xbound = xbound;
-        }
-      }
-    }
+    ConvArgs a0{};
+    a0.src1 = x; a0.C1 = Cin; a0.out = o; a0.Cout = Cout; a0.B = B; a0.H = H; a0.W = W; a0.out_scale = 1.f;
+    a0.ablate = ablate;
+    if (fused) { a0.in_scale = sc; a0.in_shift = sc + (size_t)B * Cin; a0.in_act = 1; a0.res = r; a0.bias = w; a0.out_scale = 0.70710678f; }
+    if (b3 && smode == 2 && ks == 1) { a0.in_scale = nullptr; a0.in_shift = nullptr; a0.in_act = 0; }     // raw input, as in the network's shortcut layers
+    EventTimer timer;
+    StandaloneConv s = standalone_conv(a0, b3 ? ConvPack{ConvPack::Split, smode} : (wino || wino2d) ? ConvPack{ConvPack::Wino, 2, wform}
+                                                                               : ConvPack{ConvPack::Mfma, 0, WinoForm::F23, pl.co_t}, w, ks);
+    ConvArgs& a = s.a;
+    DevBuf trace_buf;
     unsigned long long* trace_dev = nullptr;
     const size_t n_wg = (size_t)B * ((H + 7) / 8) * ((W + 31) / 32) * ((Cout + 127) / 128);
     if (abl_split & 64) {
-      trace_dev = static_cast<unsigned long long*>(dev_alloc_tmp(n_wg * 256));      // (16 words per workgroup; the Winograd kernel's trace: 32)
+      trace_buf = fresh(n_wg * 256);      // (16 words per workgroup; the Winograd kernel's trace: 32)
+      trace_dev = trace_buf.as<unsigned long long>();
       SG_CHECK(drt::memset_dev(trace_dev, 0, n_wg * 256, stream_));
       a.trace = trace_dev;
     }
@@ -984,25 +972,17 @@ class Engine {
       else launch_conv_mfma(a, ks, pl, stream_, variant);
     };
     for (int i = 0; i < 2; ++i) go();
-    drt::event_record(&e0, stream_);
+    timer.start(stream_);
     for (int i = 0; i < iters; ++i) go();
-    drt::event_record(&e1, stream_);
-    drt::event_sync(&e1);
-    const float ms = drt::event_elapsed_ms(e0, e1) / (float)iters;
+    const float ms = timer.stop_ms(stream_) / (float)iters;
     check_launch();
-    drt::event_destroy(&e0); drt::event_destroy(&e1);
     if (trace_dev) {                    // phase time stamps of the LAST launch -> $SGMSE_TRACE_OUT (binary: 16 x u64 per workgroup)
       const size_t words = wino ? 32 : 16;
       std::vector<unsigned long long> h(n_wg * words);
       SG_CHECK(drt::memcpy_d2h(h.data(), trace_dev, n_wg * words * 8, stream_));
       SG_CHECK(drt::stream_sync(stream_));
       if (const char* path = getenv("SGMSE_TRACE_OUT")) { if (FILE* f = fopen(path, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); } }
-      free_tmp(trace_dev);
     }
-    for (float* q : {x, o, r, w, pk, sc}) free_tmp(q);
-    if (pk3) free_tmp(const_cast<float*>(pk3));
-    if (bounds) free_tmp(bounds);
-    if (xbound) free_tmp(xbound);
     return ms;
   }
 
@@ -1010,22 +990,18 @@ class Engine {
   // STEPS=pmcbench.  mode 0 = read, 1 = write; bytes_per_lane 8 or 16.  Returns ms of the launch.
   float calib_stream(int mode, int bytes_per_lane, size_t total_bytes) {
     SG_REQUIRE((bytes_per_lane == 8 || bytes_per_lane == 16) && (mode == 0 || mode == 1) && total_bytes >= 4096, "calib_stream: bad arguments");
-    float* buf = static_cast<float*>(dev_alloc_tmp(total_bytes + 256));
+    const DevBuf scratch = fresh(total_bytes + 256);
+    float* buf = scratch.as<float>();
     SG_CHECK(drt::memset_dev(buf, 0, total_bytes + 256, stream_));
     const size_t nvec = total_bytes / (size_t)bytes_per_lane;
-    drt::event_t e0{}, e1{};
-    drt::event_create(&e0); drt::event_create(&e1);
-    drt::event_record(&e0, stream_);
+    EventTimer timer;
+    timer.start(stream_);
     const dim3 g(256 * 16), b(256);
     float* sink = buf + total_bytes / 4;
     if (bytes_per_lane == 8) { if (mode) DRT_LAUNCH((calib_stream_kernel<2, 1>), g, b, stream_, buf, nvec, sink); else DRT_LAUNCH((calib_stream_kernel<2, 0>), g, b, stream_, buf, nvec, sink); }
     else { if (mode) DRT_LAUNCH((calib_stream_kernel<4, 1>), g, b, stream_, buf, nvec, sink); else DRT_LAUNCH((calib_stream_kernel<4, 0>), g, b, stream_, buf, nvec, sink); }
-    drt::event_record(&e1, stream_);
-    drt::event_sync(&e1);
-    const float ms = drt::event_elapsed_ms(e0, e1);
+    const float ms = timer.stop_ms(stream_);
     check_launch();
-    drt::event_destroy(&e0); drt::event_destroy(&e1);
-    free_tmp(buf);
     return ms;
   }
 
@@ -1047,7 +1023,7 @@ class Engine {
     for (size_t i = 0; i < prof_used_; ++i) {
       ProfRec& r = prof_recs_[i];
       if (r.cls < 0) continue;                      // (a tock() without its tick())
-      const float ms = drt::event_elapsed_ms(r.a, r.b);
+      const float ms = drt::event_elapsed_ms(*r.a.get(), *r.b.get());
       prof_ms_[r.cls] += ms;
       prof_flops_[r.cls] += r.work;
       prof_n_[r.cls] += r.launches;
@@ -1058,40 +1034,20 @@ class Engine {
 
  private:
   // ---- memory helpers ------------------------------------------------------------------------------------------
-  // allocations that belong to the current weight set; released together when new weights are loaded (EMA swap, reload)
-  void* dev_alloc_w(size_t bytes) {
-    void* p = nullptr;
-    SG_CHECK(drt::malloc_dev(&p, bytes ? bytes : 256));
-    if (poison_) SG_CHECK(drt::memset_dev(p, 0xFF, bytes ? bytes : 256, stream_));
-    wowned_.push_back(p);
-    return p;
-  }
-  void free_weight_allocs() {
-    if (wowned_.empty()) return;
-    drt::stream_sync(stream_);
-    for (void* p : wowned_) drt::free_dev(p);
-    wowned_.clear();
-  }
+  // Every device buffer is a holder (dev_memory.h): a member for what persists (grow / renew), a local for scratch (fresh), an
+  // element of wset_ for what belongs to the current weight set (keep).
   // SGMSE_POISON=1 (tests): every allocation, and the activation arena before every forward, is filled with 0xFF bytes (a NaN
   // in every float), so that a kernel reading memory nobody wrote shows up as a NaN in the result instead of depending on
   // what the allocation happened to hold
-  void* dev_alloc(size_t bytes) {
-    void* p = nullptr;
-    SG_CHECK(drt::malloc_dev(&p, bytes ? bytes : 256));
-    if (poison_) SG_CHECK(drt::memset_dev(p, 0xFF, bytes ? bytes : 256, stream_));
-    owned_.push_back(p);
-    return p;
-  }
-  void* dev_alloc_tmp(size_t bytes) {
-    void* p = nullptr;
-    SG_CHECK(drt::malloc_dev(&p, bytes ? bytes : 256));
-    if (poison_) SG_CHECK(drt::memset_dev(p, 0xFF, bytes ? bytes : 256, stream_));
-    return p;
-  }
-  void free_tmp(void* p) { drt::free_dev(p); }
-  void dev_free_owned(void* p) {
-    for (size_t i = 0; i < owned_.size(); ++i) if (owned_[i] == p) { owned_.erase(owned_.begin() + i); break; }
-    drt::free_dev(p);
+  bool grow(DevBuf& b, size_t bytes) { return b.ensure(bytes, stream_, poison_); }
+  void renew(DevBuf& b, size_t bytes) { b.renew(bytes, stream_, poison_); }
+  DevBuf fresh(size_t bytes) { DevBuf b; grow(b, bytes); return b; }
+  // the current weight set: released together, behind a stream synchronisation, when new weights are loaded (EMA swap, reload)
+  template <class T = float> T* keep(DevBuf b) { wset_.push_back(std::move(b)); return wset_.back().as<T>(); }
+  void release_weights() {
+    if (wset_.empty()) return;
+    drt::stream_sync(stream_);
+    wset_.clear();
   }
   void check_launch() { SG_CHECK(drt::last_error()); }
   void require_ready() { SG_REQUIRE(weights_ready_, "weights not loaded (call sgmse_load_weights first)"); }
@@ -1128,17 +1084,17 @@ class Engine {
 
   const float2* twiddle(int n_fft) {
     auto it = twiddles_.find(n_fft);
-    if (it != twiddles_.end()) return it->second;
+    if (it != twiddles_.end()) return it->second.get();
     std::vector<float2> h(n_fft);
     for (int m = 0; m < n_fft; ++m) {
       const double ang = 2.0 * 3.14159265358979323846 * (double)m / (double)n_fft;
       h[m] = make_float2((float)cos(ang), (float)sin(ang));
     }
-    float2* d = static_cast<float2*>(dev_alloc(sizeof(float2) * n_fft));
+    DevArray<float2> d;
+    grow(d, sizeof(float2) * n_fft);
     SG_CHECK(drt::memcpy_h2d(d, h.data(), sizeof(float2) * n_fft, stream_));
     SG_CHECK(drt::stream_sync(stream_));
-    twiddles_[n_fft] = d;
-    return d;
+    return twiddles_.emplace(n_fft, std::move(d)).first->second.get();
   }
 
   const float* Wp(const std::string& name) const {
@@ -1157,22 +1113,22 @@ class Engine {
     if (pl.mfma) {
       c.co_t = pl.co_t;
       const PackArgs pa = oihw_sources(c.oihw, ks, cin, cout);
-      c.packed = pack_mfma(pa, pl.co_t, true);
-      if (pl.co_t > 32) c.packed32 = pack_mfma(pa, 32, true);
+      c.packed = keep(pack_mfma(pa, pl.co_t));
+      if (pl.co_t > 32) c.packed32 = keep(pack_mfma(pa, 32));
     }
     // fp16x2: the input scale is a per-utterance power of two derived at run time -- 3x3 layers from the bound of their GroupNorm
     // producer's output (gn_finalize_kernel), 1x1 layers (raw residual stream) from the producers' range bounds -- the stored
     // factor only undoes the weights'
     if (split_mode_ && (conv_split_eligible(ks, cin, 0, cout) || conv_thin_split_eligible(ks, cin, 0, cout))) {
       c.split_mode = split_mode_;
-      c.packed_split = pack_split(c.oihw, ks, cin, cout, c.split_mode, true, &c.split_scale);
+      c.packed_split = keep(pack_split(c.oihw, ks, cin, cout, c.split_mode, &c.split_scale));
     }
-    if (conv_thin_eligible(ks, cin, 0, cout)) c.packed_thin = pack_thin(c.oihw, cin, cout, true);
+    if (conv_thin_eligible(ks, cin, 0, cout)) c.packed_thin = keep(pack_thin(c.oihw, cin, cout));
     // the wide levels run these layers on a Winograd x fp16x2 kernel (conv_route(): use_wino): F(4,3) along the frame axis, or F(2,3) under SGMSE_WINO43=0
     // (one form per engine, decided here; the channel conditions of the two forms are the same, the width condition is a property of the level: conv_route())
     if (split_mode_ == 2 && wino_ && ks == 3 && conv_wino_eligible(cin, 0, cout, 2)) {
       c.wino_form = (wino43_ && conv_wino43_eligible(cin, 0, cout, 4)) ? WinoForm::F43 : WinoForm::F23;
-      c.packed_wino = pack_wino(c.wino_form, c.oihw, cin, cout, true, &c.wino_scale);
+      c.packed_wino = keep(pack_wino(c.wino_form, c.oihw, cin, cout, &c.wino_scale));
     }
     return c;
   }
@@ -1182,20 +1138,23 @@ class Engine {
     PackArgs pa{}; pa.src[0] = oihw; pa.nsrc = 1; pa.cout_per_src = cout; pa.io = 0; pa.cin = cin; pa.taps = ks * ks; pa.cout = cout;
     return pa;
   }
-  const float* pack_mfma(PackArgs pa, int co_t, bool weight_owned) {
+  // (the pack_* functions return a fresh buffer: the caller keeps it in the weight set, or holds it as scratch)
+  DevBuf pack_mfma(PackArgs pa, int co_t) {
     pa.co_t = co_t; pa.total = packed_weight_elems(pa.taps == 9 ? 3 : 1, pa.cin, pa.cout, co_t);
-    pa.dst = static_cast<float*>(weight_owned ? dev_alloc_w(pa.total * 4) : dev_alloc_tmp(pa.total * 4));
+    DevBuf buf = fresh(pa.total * 4);
+    pa.dst = buf.as<float>();
     DRT_LAUNCH(pack_weights_kernel, dim3((unsigned)((pa.total + 255) / 256)), dim3(256), stream_, pa);
-    return pa.dst;
+    return buf;
   }
 
   // weights in the fragment order of conv3x3_split_kernel (mode 1: bf16x3, 2: fp16x2 with the layer's power-of-two scale)
-  const float* pack_split(const float* oihw, int ks, int cin, int cout, int mode, bool weight_owned, const float** scale_out) {
+  DevBuf pack_split(const float* oihw, int ks, int cin, int cout, int mode, const float** scale_out) {
     const int taps = ks * ks;
     const size_t frags = mode == 2 ? packed_split_frags<SplitH2>(cin, cout, taps) : packed_split_frags<SplitB3>(cin, cout, taps);
     const int cout_pad = (cout + 127) / 128 * 128;
     const size_t bytes = frags * 16 + (size_t)cout_pad * 8;             // [fragments][per-channel inverse scales][scales (packing scratch)]
-    uint32_t* pk = static_cast<uint32_t*>(weight_owned ? dev_alloc_w(bytes) : dev_alloc_tmp(bytes));
+    DevBuf buf = fresh(bytes);
+    uint32_t* pk = buf.as<uint32_t>();
     PackSplitArgs pa{oihw, pk, cin, cout, frags, nullptr, taps};
     const dim3 grid((unsigned)((frags + 255) / 256));
     if (mode == 2) {
@@ -1209,24 +1168,26 @@ class Engine {
       DRT_LAUNCH(pack_weights_split_kernel<SplitB3>, grid, dim3(256), stream_, pa);
       *scale_out = nullptr;
     }
-    return reinterpret_cast<const float*>(pk);
+    return buf;
   }
 
   // weights of the C -> 4 layers as [ci][tap][4 co] (conv3x3_thin_kernel)
-  const float* pack_thin(const float* oihw, int cin, int cout, bool weight_owned) {
+  DevBuf pack_thin(const float* oihw, int cin, int cout) {
     const size_t ne = packed_thin_elems(cin);
-    float* pk = static_cast<float*>(weight_owned ? dev_alloc_w(ne * 4) : dev_alloc_tmp(ne * 4));
+    DevBuf buf = fresh(ne * 4);
+    float* pk = buf.as<float>();
     DRT_LAUNCH(pack_weights_thin_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), stream_, oihw, pk, cin, cout);
-    return pk;
+    return buf;
   }
   // weights in the fragment order of the Winograd kernel of `form`: transformed in fp64, scaled per output channel
-  const float* pack_wino(WinoForm form, const float* oihw, int cin, int cout, bool weight_owned, const float** scale_out) {
+  DevBuf pack_wino(WinoForm form, const float* oihw, int cin, int cout, const float** scale_out) {
     const bool f43 = form == WinoForm::F43, f2d = form == WinoForm::F2x2;
     const size_t frags = f43 ? packed_wino43_frags(cin, cout) : f2d ? packed_wino2d_frags(cin, cout) : packed_wino_frags(cin, cout);
     const int cout_pad = (cout + 127) / 128 * 128;
     const size_t bytes = (f43 ? packed_wino43_bytes(cin, cout) : f2d ? packed_wino2d_bytes(cin, cout) : packed_wino_bytes(cin, cout)) +
                          (size_t)cout_pad * 4;                          // [fragments][inverse scales][scales (packing scratch)]
-    uint32_t* pk = static_cast<uint32_t*>(weight_owned ? dev_alloc_w(bytes) : dev_alloc_tmp(bytes));
+    DevBuf buf = fresh(bytes);
+    uint32_t* pk = buf.as<uint32_t>();
     float* inv = reinterpret_cast<float*>(pk) + frags * 4;
     float* sc = inv + cout_pad;
     const PackWinoArgs pa{oihw, pk, cin, cout, frags};
@@ -1242,14 +1203,14 @@ class Engine {
       DRT_LAUNCH(pack_weights_wino_kernel, gp, dim3(256), stream_, pa, (const float*)sc);
     }
     *scale_out = inv;
-    return reinterpret_cast<const float*>(pk);
+    return buf;
   }
 
   // NIN weights W[cin][cout] (layers.py:549); nsrc of them concatenated along cout (fused q|k|v projection)
   ConvW make_nin(const std::string& pre, const int* which, int nsrc, int C) {
     ConvW c; c.ks = 1; c.cin = C; c.cout = nsrc * C;
-    float* tr = static_cast<float*>(dev_alloc_w((size_t)nsrc * C * C * 4));
-    float* bb = static_cast<float*>(dev_alloc_w((size_t)nsrc * C * 4));
+    float* tr = keep(fresh((size_t)nsrc * C * C * 4));
+    float* bb = keep(fresh((size_t)nsrc * C * 4));
     for (int s = 0; s < nsrc; ++s) {
       const std::string n = pre + "NIN_" + std::to_string(which[s]);
       DRT_LAUNCH(transpose_io_kernel, dim3((C * C + 255) / 256), dim3(256), stream_, Wp(n + ".W"), tr + (size_t)s * C * C, C, C);
@@ -1261,18 +1222,18 @@ class Engine {
       c.co_t = pl.co_t;
       PackArgs pa{}; pa.nsrc = nsrc; pa.cout_per_src = C; pa.io = 1; pa.cin = C; pa.taps = 1; pa.cout = c.cout;
       for (int s = 0; s < nsrc; ++s) pa.src[s] = Wp(pre + "NIN_" + std::to_string(which[s]) + ".W");
-      c.packed = pack_mfma(pa, pl.co_t, true);
+      c.packed = keep(pack_mfma(pa, pl.co_t));
       // (round 5) the 32-channel-tile layout too, as make_conv does: the attention projections sit at the 16 x 32 and 4 x 8 levels, where
       // conv() runs the fp32 layers on 32-channel tiles with chunked accumulation and, at small batches, split-K -- without this layout
       // q|k|v and the output projection stayed on 128-channel tiles: 24 / 8 workgroups running 16 serial K-stages at batch 1
       // (31 / 30 us per launch against 18 us for the 1x1 shortcut of the same size, profiles/r05_prof_dump_b1.txt)
       // (round 6: the compile-time switch of round 5's A/B is gone -- one build variant, the tested one.  Attention outputs changed in
       //  their last bits with that round: fixtures of these levels recorded before it are not bit-comparable.)
-      if (pl.co_t > 32) c.packed32 = pack_mfma(pa, 32, true);
+      if (pl.co_t > 32) c.packed32 = keep(pack_mfma(pa, 32));
     }
     if (split_mode_ && conv_split_eligible(1, C, 0, c.cout)) {
       c.split_mode = 1;
-      c.packed_split = pack_split(c.oihw, 1, C, c.cout, 1, true, &c.split_scale);
+      c.packed_split = keep(pack_split(c.oihw, 1, C, c.cout, 1, &c.split_scale));
     }
     return c;
   }
@@ -1310,7 +1271,7 @@ class Engine {
           // input channels zero-padded to one 8-channel K-stage it runs on the fp32 MFMA kernel, GroupNorm partials fused
           // (1.07 ms; 16 channels on the bf16x3 split kernel measured the same at batch 32 and twice the time at batch 1)
           constexpr int cp = 8;
-          float* w8 = static_cast<float*>(dev_alloc_w((size_t)m.cout * cp * 9 * 4));
+          float* w8 = keep(fresh((size_t)m.cout * cp * 9 * 4));
           DRT_LAUNCH(pad_cin_kernel, dim3((unsigned)(((size_t)m.cout * cp * 9 + 255) / 256)), dim3(256), stream_, Wp(p + "weight"), w8, m.cout, 4, cp, 9);
           entry8_ = make_conv(w8, Wp(p + "bias"), 3, cp, m.cout);
           entry8_idx_ = m.idx;
@@ -1323,7 +1284,7 @@ class Engine {
     }
     tot_temb_ = off;
     n_dense_ = (int)descs.size();
-    dense_descs_ = static_cast<DenseDesc*>(dev_alloc_w(sizeof(DenseDesc) * descs.size()));
+    dense_descs_ = keep<DenseDesc>(fresh(sizeof(DenseDesc) * descs.size()));
     SG_CHECK(drt::memcpy_h2d(dense_descs_, descs.data(), sizeof(DenseDesc) * descs.size(), stream_));
     SG_CHECK(drt::stream_sync(stream_));
     check_launch();
@@ -1349,42 +1310,29 @@ class Engine {
         run_forward(nullptr, 0, nullptr, 0, nullptr, B, F, T, ctl);
       }
       dry_ = false;
-      const size_t need = arena_.high_water() + (1 << 20);
-      if (need > arena_cap_) {
-        if (arena_base_) dev_free_owned(arena_base_);
-        arena_base_ = static_cast<char*>(dev_alloc(need));
-        arena_cap_ = need;
-      }
-      arena_.configure(arena_base_, arena_cap_);
+      grow(arena_buf_, arena_.high_water() + (1 << 20));
+      arena_.configure(arena_buf_.as<char>(), arena_buf_.capacity());
       const size_t n = (size_t)B * F * T;      // (a ragged batch needs at most this)
-      if (n > samp_n_) {
-        for (float2** q : {&sx_, &sxm_, &sscore_, &sy_}) { if (*q) dev_free_owned(*q); *q = static_cast<float2*>(dev_alloc(n * 8)); }
-        samp_n_ = n;
-      }
+      for (DevArray<float2>* q : {&sx_, &sxm_, &sscore_, &sy_}) grow(*q, n * 8);
       // range-bound slots: one per convolution output of the forward just dry-run
-      const size_t need_amax = (size_t)amax_next_ * B * kAmaxSpread;
       amax_slots_ = amax_next_;
-      if (need_amax > amax_pool_floats_) {
-        if (amax_pool_) dev_free_owned(amax_pool_);
-        amax_pool_ = static_cast<float*>(dev_alloc(need_amax * 4));
-        amax_pool_floats_ = need_amax;
-      }
-      if (!step_ctr_) step_ctr_ = static_cast<int*>(dev_alloc(256));
-      if (!lang_scal_) lang_scal_ = static_cast<float*>(dev_alloc(256));
-      if (lang_partial_) dev_free_owned(lang_partial_);
-      lang_partial_ = static_cast<float*>(dev_alloc((size_t)B * LANG_NBLK * 2 * 4));
+      grow(amax_pool_, (size_t)amax_next_ * B * kAmaxSpread * 4);
+      grow(step_ctr_, 256);
+      grow(lang_scal_, 256);
+      renew(lang_partial_, (size_t)B * LANG_NBLK * 2 * 4);
       shape_B_ = B; shape_F_ = F; shape_T_ = T;
     }
-    if (nrows > temb_rows_) {
+    if (nrows > temb_rows_) {      // the six time-embedding tables: sized by the rows and by this net's Dense layout, re-allocated together
       invalidate_graph();
-      if (temb_act_) { dev_free_owned(temb_act_); dev_free_owned(bias_table_); dev_free_owned(step_table_); dev_free_owned(tsteps_); dev_free_owned(coef_table_); dev_free_owned(bias_cur_); }
-      temb_rows_ = std::max(nrows, 64);
-      temb_act_ = static_cast<float*>(dev_alloc((size_t)temb_rows_ * 4 * cfg_.nf * 4));
-      bias_table_ = static_cast<float*>(dev_alloc((size_t)temb_rows_ * std::max(tot_temb_, 1) * 4));
-      bias_cur_ = static_cast<float*>(dev_alloc((size_t)std::max(tot_temb_, 1) * 4));
-      step_table_ = static_cast<float*>(dev_alloc((size_t)temb_rows_ * SC_STRIDE * 4));
-      tsteps_ = static_cast<float*>(dev_alloc((size_t)temb_rows_ * 4));
-      coef_table_ = static_cast<float*>(dev_alloc((size_t)temb_rows_ * 16));
+      temb_rows_ = 0;
+      const size_t rows = std::max(nrows, 64);
+      renew(temb_act_, rows * 4 * cfg_.nf * 4);
+      renew(bias_table_, rows * std::max(tot_temb_, 1) * 4);
+      renew(bias_cur_, (size_t)std::max(tot_temb_, 1) * 4);
+      renew(step_table_, rows * SC_STRIDE * 4);
+      renew(tsteps_, rows * 4);
+      renew(coef_table_, rows * 16);
+      temb_rows_ = (int)rows;
     }
   }
 
@@ -1394,7 +1342,7 @@ class Engine {
     SG_REQUIRE(cfg_.nf <= 256, "nf > 256 not supported by temb kernel");
     DRT_LAUNCH(temb_mlp_kernel, dim3(rows), dim3(256), stream_, ta);
     DRT_LAUNCH(temb_dense_kernel, dim3(n_dense_, rows), dim3(256), stream_, (const DenseDesc*)dense_descs_,
-               (const float*)temb_act_, 4 * cfg_.nf, bias_table_, tot_temb_);
+               (const float*)temb_act_, 4 * cfg_.nf, bias_table_.get(), tot_temb_);
     check_launch();
   }
 
@@ -1413,30 +1361,30 @@ class Engine {
     }
     if (!prof_ || prof_used_ == 0) return;
     ProfRec& r = prof_recs_[prof_used_ - 1];
-    drt::event_record(&r.b, stream_);
+    drt::event_record(r.b.get(), stream_);
     r.cls = cls; r.work = work; r.launches = launches;
     snprintf(r.note, sizeof r.note, "%s", prof_note_);
     prof_note_[0] = 0;
   }
   bool noting() const { return (prof_ && prof_dump_) || debug_sync_; }
   // one event pair per launch of a profiled forward (created on first use, reused by later profiles, destroyed with the engine)
-  struct ProfRec { drt::event_t a{}, b{}; int cls = -1; double work = 0.0; int launches = 0; char note[160] = {0}; };
+  struct ProfRec { Event a, b; int cls = -1; double work = 0.0; int launches = 0; char note[160] = {0}; };
   void tock() {
     if (lds_poison_ && !dry_ && !capturing_ && !drt::is_emulator()) {
       const int idx = lds_poison_count_++;
       if (lds_poison_at_ < 0 || idx == lds_poison_at_ || (lds_poison_upto_ && idx <= lds_poison_at_)) {
-        if (!lds_sink_) lds_sink_ = static_cast<unsigned*>(dev_alloc(256));
-        DRT_LAUNCH(lds_poison_kernel, dim3(768), dim3(256), stream_, lds_sink_, (unsigned)idx);
+        grow(lds_sink_, 256);
+        DRT_LAUNCH(lds_poison_kernel, dim3(768), dim3(256), stream_, lds_sink_.get(), (unsigned)idx);
       }
     }
     if (!prof_) return;
     if (prof_used_ == prof_recs_.size()) {
       prof_recs_.emplace_back();
-      drt::event_create(&prof_recs_.back().a); drt::event_create(&prof_recs_.back().b);
+      prof_recs_.back().a.create(); prof_recs_.back().b.create();
     }
     ProfRec& r = prof_recs_[prof_used_++];
     r.cls = -1; r.note[0] = 0;
-    drt::event_record(&r.a, stream_);
+    drt::event_record(r.a.get(), stream_);
   }
 
   Tensor new_tensor(int C, int H, int W) { Tensor t; t.C = C; t.H = H; t.W = W; t.p = arena_.alloc((size_t)C * pix_total(H, W)); return t; }
@@ -1451,12 +1399,13 @@ class Engine {
   bool ragged() const { return !rag_T_.empty(); }
   int level_of(int H) const { int l = 0; while ((cur_F_ >> l) > H && l < 30) ++l; return l; }
   int dec_W(int H) const { return std::max(1, kNominalFrames >> level_of(H)); }
-  size_t pix_total(int H, int W) const { return ragged() ? rag_pix_.at(level_of(H)) : (size_t)B_ * H * W; }
+  size_t pix_total(int H, int W) const { return ragged() ? rag_.at(level_of(H)).pix : (size_t)B_ * H * W; }
   Rag rag_of(int H) const {
     if (!ragged()) return Rag{nullptr, nullptr, nullptr};
-    const int l = level_of(H);
-    return Rag{rag_w_dev_.at(l), rag_off_dev_.at(l), rag_soff_dev_.at(l)};
+    const RagLevel& r = rag_.at(level_of(H));
+    return Rag{r.w, r.off, r.soff};
   }
+  const long long* rag_off0() const { return ragged() ? rag_[0].off.get() : nullptr; }      // first elements of the utterances in the packed tensors
   bool rag_all_mult(int H, int m) const {          // a ragged batch: is every utterance's width at this level a multiple of m?  (uniform batches: yes, the caller checks W)
     const int l = level_of(H);
     for (int t : rag_T_) if ((t >> l) % m) return false;
@@ -1472,8 +1421,7 @@ class Engine {
     int tmax = 0;
     for (int t : rag_T_) { SG_REQUIRE(t >= down && t % down == 0, "ragged batch: frame counts must be multiples of 2^(levels-1)"); tmax = std::max(tmax, t); }
     SG_REQUIRE(tmax == T, "ragged batch: T must be the largest frame count");
-    for (void* q : rag_owned_) dev_free_owned(q);
-    rag_owned_.clear(); rag_w_dev_.clear(); rag_off_dev_.clear(); rag_soff_dev_.clear(); rag_pix_.clear(); rag_cols_dev_.clear(); rag_ncols_.clear();
+    rag_.clear();
     for (int l = 0; l < L; ++l) {
       const int H = F >> l;
       std::vector<int> w(B), cols(B + 1, 0);
@@ -1484,26 +1432,23 @@ class Engine {
         soff[b + 1] = soff[b] + (long long)H * ((w[b] + 31) / 32);
         cols[b + 1] = cols[b] + (w[b] + 31) / 32;             // tile columns that exist (ConvArgs::rag_cols)
       }
-      int* wd = static_cast<int*>(dev_alloc((size_t)B * 4));
-      long long* od = static_cast<long long*>(dev_alloc((size_t)(B + 1) * 8));
-      long long* sd = static_cast<long long*>(dev_alloc((size_t)(B + 1) * 8));
-      SG_CHECK(drt::memcpy_h2d(wd, w.data(), (size_t)B * 4, stream_));
-      SG_CHECK(drt::memcpy_h2d(od, off.data(), (size_t)(B + 1) * 8, stream_));
-      SG_CHECK(drt::memcpy_h2d(sd, soff.data(), (size_t)(B + 1) * 8, stream_));
-      int* cd = static_cast<int*>(dev_alloc((size_t)(B + 1) * 4));
-      SG_CHECK(drt::memcpy_h2d(cd, cols.data(), (size_t)(B + 1) * 4, stream_));
+      RagLevel r;
+      r.pix = (size_t)off[B]; r.ncols = cols[B];
+      grow(r.w, (size_t)B * 4); grow(r.off, (size_t)(B + 1) * 8); grow(r.soff, (size_t)(B + 1) * 8); grow(r.cols, (size_t)(B + 1) * 4);
+      SG_CHECK(drt::memcpy_h2d(r.w, w.data(), (size_t)B * 4, stream_));
+      SG_CHECK(drt::memcpy_h2d(r.off, off.data(), (size_t)(B + 1) * 8, stream_));
+      SG_CHECK(drt::memcpy_h2d(r.soff, soff.data(), (size_t)(B + 1) * 8, stream_));
+      SG_CHECK(drt::memcpy_h2d(r.cols, cols.data(), (size_t)(B + 1) * 4, stream_));
       SG_CHECK(drt::stream_sync(stream_));
-      rag_owned_.push_back(cd); rag_cols_dev_.push_back(cd); rag_ncols_.push_back(cols[B]);
-      rag_owned_.push_back(wd); rag_owned_.push_back(od); rag_owned_.push_back(sd);
-      rag_w_dev_.push_back(wd); rag_off_dev_.push_back(od); rag_soff_dev_.push_back(sd);
-      rag_pix_.push_back((size_t)off[B]);
+      rag_.push_back(std::move(r));
     }
     rag_built_ = true;
   }
   std::vector<int> rag_T_;
-  std::vector<int*> rag_w_dev_; std::vector<long long*> rag_off_dev_, rag_soff_dev_; std::vector<size_t> rag_pix_;
-  std::vector<int*> rag_cols_dev_; std::vector<int> rag_ncols_;
-  std::vector<void*> rag_owned_;
+  // one U-Net level's tables: per utterance its width, first pixel, first statistics sub-tile and first tile column (B + 1 entries:
+  // prefix sums); pixels and tile columns of the whole batch
+  struct RagLevel { DevArray<int> w; DevArray<long long> off, soff; DevArray<int> cols; size_t pix = 0; int ncols = 0; };
+  std::vector<RagLevel> rag_;
   bool rag_built_ = false;
   int cur_F_ = 0;
   void drop(Tensor& t) { arena_.release(t.p); t.p = nullptr; if (t.st) { arena_.release(t.st); t.st = nullptr; } }
@@ -1605,7 +1550,7 @@ class Engine {
       const Rag rg = rag_of(a.H);
       ca.rag_w = rg.w; ca.rag_off = rg.off; ca.rag_soff = rg.soff; ca.rag_slab = (long long)w.cout * (long long)pix_total(a.H, a.W);
       ca.rag_vec_ok = rag_all_mult(a.H, 4) ? 1 : 0;
-      if (rag_prefix_) { const int l = level_of(a.H); ca.rag_cols = rag_cols_dev_.at(l); ca.rag_ncols = rag_ncols_.at(l); }
+      if (rag_prefix_) { const RagLevel& r = rag_.at(level_of(a.H)); ca.rag_cols = r.cols; ca.rag_ncols = r.ncols; }
     }
     double fl = 2.0 * B_ * (double)w.cout * Cin * w.ks * w.ks * a.H * a.W;
     if (sc) {
@@ -1638,15 +1583,15 @@ class Engine {
         SG_REQUIRE(conv_wino43_aligned(ca), "conv: unaligned source on a Winograd F(4,3) level");
         [[fallthrough]];
       case ConvFamily::Wino23:
-        ca.w = w.packed_wino; ca.co_scale = w.wino_scale; ca.xbound = xf.bound;
+        ca.w = w.packed_wino; ca.co_scale = w.wino_scale;
+        bind_bounds(ca, w.ks, xf.bound, a.amax, b ? b->amax : nullptr);
         launch_conv_wino(w.wino_form, ca, stream_, rt.rows4);
         note_split(fam == ConvFamily::Wino43 ? "wino43" : "wino");
         break;
       case ConvFamily::Split:
       case ConvFamily::SplitCoarse:
         ca.w = w.packed_split; ca.co_scale = w.split_scale;      // (null for bf16x3: no scale)
-        if (w.ks == 1 && w.split_mode == 2) { ca.amax1 = a.amax; ca.amax2 = b ? b->amax : nullptr; }
-        if (w.ks == 3 && w.split_mode == 2) ca.xbound = xf.bound;
+        if (w.split_mode == 2) bind_bounds(ca, w.ks, xf.bound, a.amax, b ? b->amax : nullptr);
         launch_conv_split(ca, w.ks, w.split_mode, stream_, rt.rows4, 0, rt.ksplit);
         note_split("split");
         break;
@@ -1809,8 +1754,8 @@ class Engine {
   bool side_enabled() const { return side_stream_on_ && B_ <= side_max_batch_; }
   bool side_active() const { return side_enabled() && !prof_ && !dry_ && !drt::is_emulator(); }
   drt::event_t* side_event() {
-    if (side_ev_next_ == side_ev_.size()) { side_ev_.emplace_back(); SG_CHECK(drt::event_create_order(&side_ev_.back())); }
-    return &side_ev_[side_ev_next_++];
+    if (side_ev_next_ == side_ev_.size()) side_ev_.emplace_back(Event::Order);
+    return side_ev_[side_ev_next_++].get();
   }
   void side_begin() {
     SG_REQUIRE(!side_open_, "side stream: nested section");
@@ -1844,7 +1789,7 @@ class Engine {
     arena_.defer_end();
   }
   drt::stream_t side_stream_{}; bool side_stream_ready_ = false, side_open_ = false, side_pending_ = false, side_swapped_ = false;
-  std::deque<drt::event_t> side_ev_; size_t side_ev_next_ = 0; drt::event_t* side_join_ev_ = nullptr;
+  std::deque<Event> side_ev_; size_t side_ev_next_ = 0; drt::event_t* side_join_ev_ = nullptr;
   bool side_stream_on_ = true; int side_max_batch_ = 8;
 
   // NCSNpp.forward (ncsnpp.py:256-419) / NCSNpp_48k.forward
@@ -1852,9 +1797,10 @@ class Engine {
                    const FwdCtl& ctl_in) {
     side_ev_next_ = 0; side_open_ = side_pending_ = false; side_join_ev_ = nullptr;
     try { run_forward_main(x, xbs, y, ybs, out, B, F, T, ctl_in); }
-    catch (...) {                 // never leave the engine on its side stream
+    catch (...) {                 // never leave the engine on its side stream, nor the arena deferring its releases
       if (side_swapped_) { std::swap(stream_, side_stream_); side_swapped_ = false; }
       side_open_ = side_pending_ = false; side_join_ev_ = nullptr;
+      arena_.reset();             // (also takes back whatever the failed forward still held)
       throw;
     }
   }
@@ -1865,17 +1811,17 @@ class Engine {
     if (!dry_ && ctl.step_ptr && ctl.bias_table && ctl.bias_bstride == 0 && tot_temb_ > 0) {
       // sampler loop: this step's bias row into a fixed buffer (bias_select_kernel), the convolutions read it without indirection
       DRT_LAUNCH(bias_select_kernel, dim3((tot_temb_ + 255) / 256), dim3(256), stream_, ctl.bias_table, ctl.bias_sstride, ctl.step_ptr,
-                 bias_cur_, tot_temb_);
+                 bias_cur_.get(), tot_temb_);
       ctl.bias_table = bias_cur_; ctl.bias_sstride = 0; ctl.bias_step = nullptr;
     }
     B_ = B;
     cur_F_ = F;
     amax_next_ = 0;
     lds_poison_count_ = 0;
-    if (!dry_ && poison_ && arena_base_) SG_CHECK(drt::memset_dev(arena_base_, 0xFF, arena_cap_, stream_));
+    if (!dry_ && poison_ && arena_buf_.capacity()) SG_CHECK(drt::memset_dev(arena_buf_.as<char>(), 0xFF, arena_buf_.capacity(), stream_));
     if (!dry_ && amax_pool_) {
       const int n = amax_slots_ * B * kAmaxSpread;
-      DRT_LAUNCH(zero_floats_kernel, dim3((n + 255) / 256), dim3(256), stream_, amax_pool_, n);
+      DRT_LAUNCH(zero_floats_kernel, dim3((n + 255) / 256), dim3(256), stream_, amax_pool_.get(), n);
     }
     const NetCfg& c = cfg_;
     const int L = c.n_levels;
@@ -2015,22 +1961,15 @@ class Engine {
   // behind the previous use's copies has passed (for a new call it has, long before: the copies are the first thing a call
   // enqueues); commit(stream) records that event behind the copies just enqueued on `stream`.
   struct HostStage {
-    char* hstage_ = nullptr; size_t cap_ = 0; drt::event_t ev_{}; bool ev_init_ = false, pending_ = false;
-    ~HostStage() { if (hstage_) drt::free_host(hstage_); if (ev_init_) drt::event_destroy(&ev_); }
+    PinnedArray<char> buf_; Event ev_; bool pending_ = false;
     char* acquire(size_t n) {
-      if (pending_) { SG_CHECK(drt::event_sync(&ev_)); pending_ = false; }
-      if (n > cap_) {
-        if (hstage_) drt::free_host(hstage_);
-        hstage_ = nullptr; cap_ = 0;
-        n = std::max(n, size_t(1) << 16);
-        SG_CHECK(drt::malloc_host(reinterpret_cast<void**>(&hstage_), n));
-        cap_ = n;
-      }
-      return hstage_;
+      if (pending_) { SG_CHECK(drt::event_sync(ev_.get())); pending_ = false; }
+      buf_.ensure(std::max(n, size_t(1) << 16));
+      return buf_;
     }
     void commit(drt::stream_t stream) {
-      if (!ev_init_) { SG_CHECK(drt::event_create(&ev_)); ev_init_ = true; }
-      SG_CHECK(drt::event_record(&ev_, stream));
+      ev_.create();
+      SG_CHECK(drt::event_record(ev_.get(), stream));
       pending_ = true;
     }
   } stage_;
@@ -2040,7 +1979,7 @@ class Engine {
   const unsigned long long* upload_tables(const std::vector<float>& tab, const std::vector<float>& tv, const std::vector<float>& cf,
                                           unsigned long long seed, int B) {
     SG_REQUIRE(B + 1 <= kMaxStreams, "batch too large for the noise-stream table");
-    if (!seed_dev_) seed_dev_ = static_cast<unsigned long long*>(dev_alloc((size_t)kMaxStreams * 8));
+    grow(seed_dev_, (size_t)kMaxStreams * 8);
     const size_t nb_seed = ((size_t)B + 1) * 8, nb_tab = tab.size() * 4, nb_tv = tv.size() * 4, nb_cf = cf.size() * 4;
     char* q = stage_.acquire(nb_seed + nb_tab + nb_tv + nb_cf);
     unsigned long long* hs = reinterpret_cast<unsigned long long*>(q);
@@ -2056,11 +1995,11 @@ class Engine {
     SG_CHECK(drt::memcpy_h2d(tsteps_, q + nb_tab, nb_tv, stream_));
     if (nb_cf) SG_CHECK(drt::memcpy_h2d(coef_table_, q + nb_tab + nb_tv, nb_cf, stream_));
     stage_.commit(stream_);
-    return seed_dev_;
+    return seed_dev_.get();
   }
   static constexpr int kMaxStreams = 4096;
   std::vector<unsigned long long> streams_next_;
-  unsigned long long* seed_dev_ = nullptr;
+  DevArray<unsigned long long> seed_dev_;
   int graph_captures_ = 0;
 
   int device_;
@@ -2068,17 +2007,16 @@ class Engine {
   NetCfg cfg_;
   std::vector<Mod> layout_;
   std::map<std::string, const float*> W_;
-  float* blob_ = nullptr; size_t blob_elems_ = 0;
   std::map<int, ResW> res_;
   std::map<int, AttnW> attn_;
   std::map<int, ConvW> conv_;
   std::map<int, std::pair<const float*, const float*>> gn_;
   DenseDesc* dense_descs_ = nullptr; int n_dense_ = 0; int tot_temb_ = 0;
   bool weights_ready_ = false;
-  std::vector<void*> owned_, wowned_;
-  std::map<int, const float2*> twiddles_;
+  std::vector<DevBuf> wset_;
+  std::map<int, DevArray<float2>> twiddles_;
 
-  Arena arena_; char* arena_base_ = nullptr; size_t arena_cap_ = 0;
+  Arena arena_; DevBuf arena_buf_;
   bool dry_ = false;
   // Runtime switches, re-read from the environment at every configure / weight load (so one process can compare settings).
   // User-facing: SGMSE_CONV_SPLIT, SGMSE_WINO, SGMSE_WINO43, SGMSE_CONV_XCD_MAP, SGMSE_RAGGED_PREFIX, SGMSE_DEBUG_SYNC,
@@ -2119,7 +2057,7 @@ class Engine {
     poison_ = flag("SGMSE_POISON", false);               // NaN patterns in every allocation and in the arena before every forward
   }
   // per-forward range-bound slots ([B][kAmaxSpread] floats each), handed out in program order; counted by the dry run
-  float* amax_pool_ = nullptr; size_t amax_pool_floats_ = 0; int amax_slots_ = 0, amax_next_ = 0;
+  DevArray<float> amax_pool_; int amax_slots_ = 0, amax_next_ = 0;
   float* next_amax() {
     const int i = amax_next_++;
     // dry run: a fake address (never dereferenced), non-null so that the kernel-family decisions that ask "is the bound known?"
@@ -2136,7 +2074,7 @@ class Engine {
   bool poison_ = false, debug_sync_ = false, conv_xcd_map_ = true, rag_prefix_ = true, wino_ = true, wino43_ = true;
   long wino_min_tiles_ = 32;
   int nofold_levels_ = 0;
-  bool lds_poison_ = false, lds_poison_upto_ = false; int lds_poison_at_ = -1, lds_poison_count_ = 0; unsigned* lds_sink_ = nullptr;
+  bool lds_poison_ = false, lds_poison_upto_ = false; int lds_poison_at_ = -1, lds_poison_count_ = 0; DevArray<unsigned> lds_sink_;
   static constexpr long coarse_splitk_div_ = 4, chunk_max_tiles_ = 8;      // (profiles/r02_chunk_splitk.txt)
   int split_mode_ = SGMSE_CONV_SPLIT_DEFAULT;
   bool prof_dump_ = false;
@@ -2144,18 +2082,17 @@ class Engine {
   static constexpr bool fir_scalar_ = false;      // (per-pixel FIR kernels everywhere: a round-1 measurement switch)
   bool fuse_gn_stats_ = true;
   int B_ = 0, shape_B_ = 0, shape_F_ = 0, shape_T_ = 0;
-  float2 *sx_ = nullptr, *sxm_ = nullptr, *sscore_ = nullptr, *sy_ = nullptr; size_t samp_n_ = 0;
-  int* step_ctr_ = nullptr;
-  float *lang_partial_ = nullptr, *lang_scal_ = nullptr;
-  float* bias_cur_ = nullptr;
-  float *temb_act_ = nullptr, *bias_table_ = nullptr, *step_table_ = nullptr, *tsteps_ = nullptr, *coef_table_ = nullptr; int temb_rows_ = 0;
+  DevArray<float2> sx_, sxm_, sscore_, sy_;
+  DevArray<int> step_ctr_;
+  DevArray<float> lang_partial_, lang_scal_;
+  DevArray<float> bias_cur_, temb_act_, bias_table_, step_table_, tsteps_, coef_table_; int temb_rows_ = 0;
   drt::graph_t graph_{}; bool graph_valid_ = false; GraphKey graph_key_{};
   int nfe_ = 0;
-  // adaptive ODE sampler (ode_run): slopes K_0..K_6, stage input; scalar table, reduction buffers and the pinned results for ode_cap_
-  // groups; last run's controllers (one per group) and round statistics
-  float2* ode_k_[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; float2* ode_xs_ = nullptr; size_t ode_n_ = 0;
+  // adaptive ODE sampler (ode_run): slopes K_0..K_6, stage input; scalar table, reduction buffers and the pinned results for the
+  // largest number of groups so far; last run's controllers (one per group) and round statistics
+  DevArray<float2> ode_k_[7], ode_xs_;
   static constexpr int kOdeEachMaxB = 1024;
-  double *ode_table_ = nullptr, *ode_partial_ = nullptr, *ode_result_ = nullptr, *ode_host_ = nullptr; int ode_cap_ = 0;
+  DevArray<double> ode_table_, ode_partial_, ode_result_; PinnedArray<double> ode_host_;
   std::vector<OdeControl> ode_ctl_; int ode_rounds_ = 0, ode_wasted_ = 0;
   bool prof_ = false; std::vector<ProfRec> prof_recs_; size_t prof_used_ = 0; float prof_ms_[TC_COUNT]; double prof_flops_[TC_COUNT]; int prof_n_[TC_COUNT];
 };
