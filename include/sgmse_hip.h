@@ -54,7 +54,9 @@ typedef struct {
 typedef struct {
   int N;
   int corrector;          /* 0 'none' (correctors.py:85-94), 1 'ald' (correctors.py:60-81), 2 'langevin' (correctors.py:37-56:
-                             step size from batch-mean norms of score and noise) */
+                             step size from batch-mean norms of score and noise; refused by a ragged context), 3 'langevin' with the
+                             step size PER UTTERANCE, 2 (snr ||z_b|| / ||score_b||)^2: utterance b gets what value 2 gives it in a
+                             batch of its own (the reference's one-file-at-a-time loop), uniform and ragged batches */
   int corrector_steps;
   int predictor;          /* 0 'none', 1 'reverse_diffusion' (predictors.py:56-65) */
   int probability_flow;   /* 1: fixed-step PF-ODE Euler step (sdes.py:130-135 with probability_flow=True), no noise */
@@ -67,7 +69,8 @@ typedef struct {
    * (model.py:307-310): in_scale 1, alpha 0, beta -1.  ncsnpp_v2 models: in_scale = c_in(t); 'score_matching': alpha =
    * c_skip(t), beta = c_out(t)*s(t); 'denoiser': alpha = -1/std(t)^2, beta = s(t)/std(t)^2; s = network_scaling. */
   const float* in_scale; const float* score_alpha; const float* score_beta;
-  float snr;              /* 'langevin' only: r in step = 2 (r * mean||z|| / mean||score||)^2 ('ald' has it folded into ald_eps) */
+  float snr;              /* 'langevin' only: r in step = 2 (r * mean||z|| / mean||score||)^2; corrector 3: the utterance's own norms
+                             ('ald' has it folded into ald_eps) */
   int use_graph;          /* 1: capture one predictor-corrector step as a hipGraph and replay it N times */
 } sgmse_sampler_cfg;
 
@@ -96,7 +99,8 @@ int sgmse_ncsnpp_forward(sgmse_ctx* ctx, const void* xy, const float* t, void* o
 /* -- get_pc_sampler(...)() (sampling/__init__.py:52-68) with score_fn = ScoreModel.forward (model.py:307-310) --
  * Y, out: complex64 [B][1][F][T].  noise: complex64 [1 + N*draws_per_step][B][1][F][T] standard-normal draws in the
  * reference's call order (prior, then per step: corrector draws, predictor draw), or NULL for the in-kernel Philox
- * stream seeded by `seed`.  *nfe receives N*(corrector_steps+1). */
+ * stream seeded by `seed`.  A ragged context (sgmse_set_frames) takes PACKED Y / out and noise [1 + N*draws_per_step][sum_b F*T_b].
+ * *nfe receives N*(corrector_steps+1). */
 int sgmse_pc_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int T, const sgmse_sampler_cfg* cfg,
                     const void* noise, unsigned long long seed, int* nfe);
 
@@ -104,7 +108,9 @@ int sgmse_pc_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int 
  *    x_0 = y; for i in 0..N-1:  x <- w_prev[i] x + w_est[i] model(x, y, t[i]) + w_y[i] y + w_z[i] z_i.  Host arrays [N] computed
  *    by the caller from SBVESDE._sigmas_alphas (sdes.py:276-288) with the reference's expressions (t = linspace(T, eps, N+1)[1:]);
  *    'ode': w_z = 0; 'sde' (stochastic = 1): w_y = 0, one draw per step, noise complex64 [N][B][1][F][T] or NULL (Philox).
- *    model = ScoreModel.forward with loss_type 'data_prediction': in_scale / score_alpha / score_beta as in sgmse_sampler_cfg. */
+ *    model = ScoreModel.forward with loss_type 'data_prediction': in_scale / score_alpha / score_beta as in sgmse_sampler_cfg.
+ *    Honours sgmse_set_frames: a ragged context takes T = max_b T_b, PACKED Y / out and noise [N][sum_b F*T_b]; every step is
+ *    element-wise apart from the network, so an utterance's result is bit-identical to its single-utterance call. */
 int sgmse_sb_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int T, int N, const float* t, const float* w_prev,
                     const float* w_est, const float* w_y, const float* w_z, const float* in_scale, const float* score_alpha,
                     const float* score_beta, int stochastic, const void* noise, unsigned long long seed, int use_graph, int* nfe);
@@ -236,13 +242,17 @@ int sgmse_arena_bytes(sgmse_ctx* ctx, long long* out);
  * global generator state, sdes.py:229, correctors.py:74, predictors.py:62). */
 int sgmse_set_noise_streams(sgmse_ctx* ctx, const unsigned long long* ids, int n);
 /* Ragged batches: frames[b] = number of spectrogram frames T_b of utterance b (host array; each a multiple of 2^(levels-1), i.e.
- * of 64 -- what pad_spec produces) for ALL FOLLOWING sgmse_ncsnpp_forward / sgmse_pc_sample calls of batch size n, until the next
+ * of 64 -- what pad_spec produces) for ALL FOLLOWING sgmse_ncsnpp_forward / sgmse_pc_sample / sgmse_sb_sample / sgmse_ode_sample_each calls of batch size n, until the next
  * call (n = 0: uniform batches again).  Those calls then take T = max_b T_b and PACKED tensors: utterance after utterance, each
  * with its own row stride -- xy: [2][F][T_b] per utterance, y / the results: [F][T_b] per utterance (sum_b F*T_b complex elements).
  * An utterance's result is bit-identical to the one its own single-utterance call gives (every kernel addresses an utterance's
  * block exactly as in that call; which kernel family a layer uses depends on the U-Net level only, never on T), so a corpus of
- * mixed lengths runs in full batches.  In-kernel noise only (noise == NULL), correctors "ald" / "none"; the Langevin corrector
- * couples the utterances of a batch (correctors.py:50-52) and the Schroedinger-bridge sampler are not supported.
+ * mixed lengths runs in full batches.  Supported: the predictor-corrector sampler with correctors 'none', 'ald' and 'langevin'
+ * per utterance (corrector = 3), the Schroedinger-bridge sampler and the adaptive solver with per-utterance step control; noise
+ * in-kernel (noise == NULL: utterance b draws from its stream id and the element index inside the utterance) or replayed, then
+ * PACKED like the results: [ndraws][sum_b F*T_b], draw-major, the utterances of a draw in batch order.  Not supported, because they
+ * couple the utterances of a batch: 'langevin' with the batch-mean step size (corrector = 2, correctors.py:50-52) and
+ * sgmse_ode_sample (one error norm over the batch).
  * Replaces the one-file-at-a-time loop of enhancement.py:57-103. */
 int sgmse_set_frames(sgmse_ctx* ctx, const int* frames, int n);
 /* how many times this context captured + instantiated a sampler step as a hipGraph (a run over many batches of one shape and

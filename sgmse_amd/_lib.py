@@ -235,6 +235,18 @@ class Context:
         frames, F_ = _ragged_geometry(items, planes, what)
         return torch.cat([check_tensor(v, what, torch.complex64, self.device).reshape(-1) for v in items]), frames, F_
 
+    def _pack_ragged_noise(self, noise, frames, F_: int, need: int):
+        """Replayed noise of a ragged batch (a list of [ndraws,1,F,T_b] tensors, one per utterance, ndraws >= ``need``) as the library
+        takes it: flat [ndraws][sum_b F*T_b], draw-major, the utterances of a draw packed in batch order."""
+        if not isinstance(noise, (list, tuple)) or len(noise) != len(frames):
+            raise ValueError(f"the replayed noise of a ragged batch is a list of {len(frames)} tensors [ndraws,1,F,T_b], one per utterance")
+        nd = int(noise[0].shape[0]) if noise[0].dim() == 4 else -1
+        for i, (v, T_b) in enumerate(zip(noise, frames)):
+            if v.dim() != 4 or tuple(v.shape) != (nd, 1, F_, T_b) or nd < need:
+                raise ValueError(f"ragged batch: noise[{i}] must be [ndraws >= {need},1,{F_},{T_b}] complex64 with one ndraws for all "
+                                 f"utterances, got {tuple(v.shape)}")
+        return torch.cat([check_tensor(v, "noise", torch.complex64, self.device).reshape(nd, -1) for v in noise], dim=1).contiguous()
+
     def _take_streams(self, streams, B: int) -> None:
         """``streams`` of a sampler call (None: the default ids): checked against the batch and handed to the library."""
         if streams is not None:
@@ -332,13 +344,17 @@ class Context:
 
     def pc_sample(self, Y: torch.Tensor, table: Dict[str, torch.Tensor], *, theta: float, std1: float,
                   corrector: str, corrector_steps: int, predictor: str, probability_flow: bool, denoise: bool,
-                  noise: Optional[torch.Tensor], seed: int, use_graph: bool = True, affine=None, snr: float = 0.0, streams=None):
+                  noise: Optional[torch.Tensor], seed: int, use_graph: bool = True, affine=None, snr: float = 0.0, streams=None,
+                  corrector_scope: str = "batch"):
         """``affine``: optional (in_scale, score_alpha, score_beta) fp32 tensors of length N: the score wrapper of
-        ScoreModel.forward's new-code branch (ncsnpp_v2); None = old-code branch (score = -F)."""
+        ScoreModel.forward's new-code branch (ncsnpp_v2); None = old-code branch (score = -F).  ``corrector_scope``: 'batch' --
+        the 'langevin' corrector takes its step size from the batch-mean norms (the reference) -- or 'utterance': from each
+        utterance's own norms, what that utterance gets in a batch of its own (uniform and ragged batches).  ``noise`` of a ragged
+        batch: a list of [ndraws,1,F,T_b] tensors, one per utterance."""
+        if corrector_scope not in ("batch", "utterance"):
+            raise ValueError(f"corrector_scope must be 'batch' or 'utterance', got {corrector_scope!r}")
         frames = None
         if isinstance(Y, (list, tuple)):       # ragged batch: utterances [F,T_b] (or [1,F,T_b]) of different lengths, see set_frames
-            if noise is not None:
-                raise ValueError("ragged batches use in-kernel noise only")
             B = len(Y)
             Y, frames, F_ = self._pack_ragged(Y, 1, "y")
             T = max(frames)
@@ -351,6 +367,8 @@ class Context:
         cfg = SamplerCfgC()
         cfg.N = N
         cfg.corrector = {"none": 0, "ald": 1, "langevin": 2}[corrector]
+        if corrector == "langevin" and corrector_scope == "utterance":
+            cfg.corrector = 3
         cfg.snr = float(snr)
         cfg.corrector_steps = int(corrector_steps)
         cfg.predictor = {"none": 0, "reverse_diffusion": 1}[predictor]
@@ -366,9 +384,12 @@ class Context:
                 keep[k] = v
                 setattr(cfg, k, C.cast(v.data_ptr(), C.POINTER(C.c_float)))
         if noise is not None:
-            noise = check_tensor(noise, "noise", torch.complex64, self.device)
             ncorr = cfg.corrector_steps if cfg.corrector else 0
             need = 1 + N * (ncorr + (1 if (cfg.predictor == 1 and not probability_flow) else 0))
+        if noise is not None and frames is not None:
+            noise = self._pack_ragged_noise(noise, frames, F_, need)
+        elif noise is not None:
+            noise = check_tensor(noise, "noise", torch.complex64, self.device)
             if noise.shape[0] < need or tuple(noise.shape[1:]) != tuple(Y.shape):
                 raise ValueError(f"noise must be [{need},{B},1,{F_},{T}] complex64, got {tuple(noise.shape)}")
         out = torch.empty_like(Y)
@@ -389,14 +410,26 @@ class Context:
 
     def sb_sample(self, Y: torch.Tensor, table: Dict[str, torch.Tensor], *, stochastic: bool, noise: Optional[torch.Tensor],
                   seed: int, affine=None, use_graph: bool = True, streams=None):
-        """Schroedinger-bridge sampler; table: fp32 tensors t, w_prev, w_est, w_y, w_z of length N."""
-        Y = check_tensor(Y, "y", torch.complex64, self.device)
-        B, _, F_, T = Y.shape
+        """Schroedinger-bridge sampler; table: fp32 tensors t, w_prev, w_est, w_y, w_z of length N.  ``Y``: [B,1,F,T], or a ragged list
+        of [F,T_b] / [1,F,T_b] spectrograms (``set_frames``; the samples come back as a list of [1,F,T_b], ``noise`` is then a list of
+        [ndraws,1,F,T_b] tensors)."""
+        frames = None
+        if isinstance(Y, (list, tuple)):
+            B = len(Y)
+            Y, frames, F_ = self._pack_ragged(Y, 1, "y")
+            T = max(frames)
+        else:
+            Y = check_tensor(Y, "y", torch.complex64, self.device)
+            if Y.dim() != 4 or Y.shape[1] != 1:
+                raise ValueError(f"expected y of shape [B,1,F,T], got {tuple(Y.shape)}")
+            B, _, F_, T = Y.shape
         N = int(table["t"].numel())
         fp = lambda v: C.cast(v.data_ptr(), C.POINTER(_F))
         keep = [table[k].detach().to("cpu", torch.float32).contiguous() for k in ("t", "w_prev", "w_est", "w_y", "w_z")]
         aff = _host_rows(affine, N)
-        if noise is not None:
+        if noise is not None and frames is not None:
+            noise = self._pack_ragged_noise(noise, frames, F_, N)
+        elif noise is not None:
             noise = check_tensor(noise, "noise", torch.complex64, self.device)
             if noise.shape[0] < N or tuple(noise.shape[1:]) != tuple(Y.shape):
                 raise ValueError(f"noise must be [{N},{B},1,{F_},{T}] complex64, got {tuple(noise.shape)}")
@@ -406,14 +439,14 @@ class Context:
 
         def run():
             self.use_current_stream()
-            self.set_frames([])
+            self.set_frames(frames if frames is not None else [])
             self.check(self.lib.sgmse_sb_sample(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, N, *[fp(v) for v in keep],
                                                 *[None if v is None else fp(v) for v in aff], int(bool(stochastic)), ptr(noise),
                                                 C.c_ulonglong(seed & (2 ** 64 - 1)), int(bool(use_graph)), C.byref(nfe)))
 
         self._with_capturable_stream(run, use_graph)
         self._keep["sb"] = (noise, keep, aff)
-        return out, nfe.value
+        return (out if frames is None else _unpack_ragged(out, frames, F_)), nfe.value
 
     def ode_sample(self, Y: torch.Tensor, *, theta: float, sigma_min: float, sigma_max: float, std1: float, t_end: float, eps: float,
                    rtol: float, atol: float, first_step: float = 0.0, max_step: float = 0.0, noise: Optional[torch.Tensor] = None,

@@ -110,7 +110,7 @@ int sgmse_pc_sample(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, int 
                     const void* noise, unsigned long long seed, int* nfe) {
   SG_ARG(ctx, Y && out && cfg && B > 0 && F > 0 && T > 0, "null pointer or non-positive shape");
   SG_ARG(ctx, cfg->N >= 1, "N must be >= 1");
-  SG_ARG(ctx, cfg->corrector >= 0 && cfg->corrector <= 2, "corrector must be none, ald or langevin");
+  SG_ARG(ctx, cfg->corrector >= 0 && cfg->corrector <= 3, "corrector must be none, ald, langevin or langevin per utterance");
   SG_ARG(ctx, cfg->predictor == 0 || cfg->predictor == 1, "predictor must be none or reverse_diffusion");
   SG_ARG(ctx, cfg->corrector == 0 || cfg->corrector_steps >= 1, "corrector_steps must be >= 1");
   return sg_guard(ctx, [&](sgmse::Engine& e) {

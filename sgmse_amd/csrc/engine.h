@@ -438,8 +438,8 @@ class Engine {
     SG_REQUIRE(sc.N >= 1 && sc.t && sc.dt && sc.G && sc.G2, "pc_sample: step table missing");
     SG_REQUIRE(sc.corrector != 1 || (sc.ald_eps && sc.ald_noise), "pc_sample: ALD table missing");
     ensure_shape(B, F, T, sc.N);
-    SG_REQUIRE(!ragged() || sc.corrector != 2, "ragged batches: the Langevin corrector couples the utterances of a batch (correctors.py:50-52) and is not supported");
-    SG_REQUIRE(!ragged() || !noise, "ragged batches: replayed noise is not supported (in-kernel noise only)");
+    SG_REQUIRE(!ragged() || sc.corrector != 2, "ragged batches: the Langevin corrector with the step size of the batch couples the utterances (correctors.py:50-52) "
+                                               "and is not supported; corrector = 3 takes the step size per utterance");
     const size_t n = ragged() ? rag_[0].pix : (size_t)B * F * T;     // complex elements of Y / the result, utterance after utterance
     const StepSetup st = begin_steps("pc_sample", Y, n, B, sc.N, seed, [&](int i, float* r) {
       r[SC_T] = sc.t[i]; r[SC_DT] = sc.dt[i]; r[SC_G] = sc.G[i]; r[SC_G2] = sc.G2[i];
@@ -448,6 +448,7 @@ class Engine {
     const FwdCtl& ctl = st.ctl;
 
     const int ncorr = sc.corrector ? sc.corrector_steps : 0;
+    const bool langevin = sc.corrector == 2 || sc.corrector == 3;       // 3: step size per utterance (lang_scal_: [B][2])
     const bool pred_noise = sc.predictor == 1 && !sc.probability_flow;
     const int draws_per_step = ncorr + (pred_noise ? 1 : 0);
 
@@ -469,7 +470,11 @@ class Engine {
         arena_.reset();
         run_forward(sx_, FT, sy_, FT, sscore_, B, F, T, ctl);
         SamplerArgs a = sa; a.draw_base = 1 + cs; a.draw_per_step = draws_per_step;
-        if (sc.corrector == 2) {
+        if (sc.corrector == 3) {
+          DRT_LAUNCH(sampler_langevin_norms_each_kernel, dim3(LANG_NBLK, B), dim3(256), stream_, a);
+          DRT_LAUNCH(sampler_langevin_scalars_each_kernel, dim3(1), dim3(64), stream_, a);
+          DRT_LAUNCH(sampler_langevin_each_kernel, eg, dim3(256), stream_, a);
+        } else if (sc.corrector == 2) {
           DRT_LAUNCH(sampler_langevin_norms_kernel, dim3(LANG_NBLK, B), dim3(256), stream_, a);
           DRT_LAUNCH(sampler_langevin_scalars_kernel, dim3(1), dim3(64), stream_, a);
           DRT_LAUNCH(sampler_langevin_kernel, eg, dim3(256), stream_, a);
@@ -488,7 +493,7 @@ class Engine {
       DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_.get());
     };
     run_steps(sc.N, GraphKey{B, F, T, sc.corrector, ncorr, sc.predictor, sc.probability_flow + (ctl.coef ? 2 : 0), (const void*)sy_, (const void*)noise,
-                             sc.theta + 1000.f * sc.snr * (sc.corrector == 2), draws_per_step},      // (set_frames invalidates the graph itself)
+                             sc.theta + 1000.f * sc.snr * langevin, draws_per_step},      // (set_frames invalidates the graph itself)
               sc.use_graph, step_body);
     SG_CHECK(drt::memcpy_d2d(out, sc.denoise ? sxm_ : sx_, n * 8, stream_));
     nfe_ = sc.N * (ncorr + 1);   // the reference counts N*(corrector.n_steps+1) whatever the predictor (sampling/__init__.py:67)
@@ -500,9 +505,8 @@ class Engine {
                  const float2* noise, unsigned long long seed, int use_graph) {
     require_ready();
     SG_REQUIRE(N >= 1 && t && w_prev && w_est && w_y && w_z, "sb_sample: step table missing");
-    SG_REQUIRE(!ragged(), "ragged batches: not supported by the Schroedinger-bridge sampler");
     ensure_shape(B, F, T, N);
-    const size_t n = (size_t)B * F * T;
+    const size_t n = ragged() ? rag_[0].pix : (size_t)B * F * T;     // complex elements of Y / the result, utterance after utterance
     const StepSetup st = begin_steps("sb_sample", Y, n, B, N, seed, [&](int i, float* r) {
       r[SC_T] = t[i]; r[SB_WPREV] = w_prev[i]; r[SB_WEST] = w_est[i]; r[SB_WY] = w_y[i]; r[SB_WZ] = w_z[i];
     }, in_scale, alpha, beta);
@@ -513,9 +517,9 @@ class Engine {
     SamplerArgs sa{};
     sa.x = sx_; sa.x_mean = sxm_; sa.y = sy_; sa.score = sscore_; sa.noise = noise; sa.seed = st.seed;
     sa.table = step_table_; sa.step_ptr = step_ctr_; sa.n = (int)n; sa.add_noise = stochastic ? 1 : 0; sa.B = B; sa.per = F * T;
-    sa.draw_base = 0; sa.draw_per_step = 1;
+    sa.draw_base = 0; sa.draw_per_step = 1; sa.rag_off = rag_off0();
     const dim3 eg((unsigned)((n + 255) / 256));
-    const long long FT = (long long)F * T;
+    const long long FT = ragged() ? 1 : (long long)F * T;          // batch stride of x / y (ragged: multiplier of the utterance's offset)
     auto step_body = [&]() {
       arena_.reset();
       run_forward(sx_, FT, sy_, FT, sscore_, B, F, T, ctl);
@@ -1318,7 +1322,7 @@ class Engine {
       amax_slots_ = amax_next_;
       grow(amax_pool_, (size_t)amax_next_ * B * kAmaxSpread * 4);
       grow(step_ctr_, 256);
-      grow(lang_scal_, 256);
+      grow(lang_scal_, std::max<size_t>(256, (size_t)B * 2 * 4));      // {step, sqrt(2 step)}: one pair, or one per utterance
       renew(lang_partial_, (size_t)B * LANG_NBLK * 2 * 4);
       shape_B_ = B; shape_F_ = F; shape_T_ = T;
     }

@@ -370,7 +370,7 @@ __device__ __forceinline__ float2 philox_cnormal(unsigned long long seed, unsign
 
 struct SamplerArgs {
   float2* x; float2* x_mean; const float2* y; const float2* score;
-  const float2* noise;       // replayed noise [ndraws][B*FT] or null (Philox)
+  const float2* noise;       // replayed noise [ndraws][n] (n = B*FT; ragged: the packed utterances) or null (Philox)
   // device words: seed[0] = the Philox seed (data, not a kernel argument, so a captured step serves every seed), seed[1 + b] =
   // the noise-stream id of utterance b.  An utterance's draws depend on (seed, stream id, element index INSIDE the utterance,
   // draw): with stream ids that name the utterance (the directory script: index in the file list) its noise, and with it the
@@ -385,19 +385,34 @@ struct SamplerArgs {
   // LangevinCorrector (correctors.py:44-56): step size from batch-mean norms
   float snr; int B; int per;        // per = FT (elements per utterance)
   float* partial;                   // [B][LANG_NBLK][2] partial sums of |grad|^2, |z|^2
-  float* lang;                      // [2]: step_size, sqrt(2*step_size)
+  float* lang;                      // [2]: step_size, sqrt(2*step_size); per-utterance form: [B][2]
   const long long* rag_off; // ragged batch: [B + 1] element prefix of the packed utterances (null: B utterances of `per` elements)
 };
 
-__device__ __forceinline__ float2 sampler_noise(const SamplerArgs& p, int i, int draw) {
-  if (p.noise) return p.noise[(size_t)draw * p.n + i];
-  if (p.rag_off) {            // the utterance this element belongs to: last b with rag_off[b] <= i
+// the utterance packed element i belongs to (ragged: the last b with rag_off[b] <= i) and, in *first, that utterance's first element
+__device__ __forceinline__ int sampler_utt(const SamplerArgs& p, int i, long long* first) {
+  if (p.rag_off) {
     int lo = 0, hi = p.B;
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (p.rag_off[mid] <= (long long)i) lo = mid; else hi = mid; }
-    return philox_cnormal(p.seed[0], (unsigned long long)((long long)i - p.rag_off[lo]), (uint32_t)draw, p.seed[1 + lo]);
+    *first = p.rag_off[lo];
+    return lo;
   }
   const int b = i / p.per;
-  return philox_cnormal(p.seed[0], (unsigned long long)(i - b * p.per), (uint32_t)draw, p.seed[1 + b]);
+  *first = (long long)b * p.per;
+  return b;
+}
+
+// the draw of element i, which lies in utterance b starting at `first`
+__device__ __forceinline__ float2 sampler_noise_of(const SamplerArgs& p, int i, int draw, int b, long long first) {
+  if (p.noise) return p.noise[(size_t)draw * p.n + i];
+  return philox_cnormal(p.seed[0], (unsigned long long)((long long)i - first), (uint32_t)draw, p.seed[1 + b]);
+}
+
+__device__ __forceinline__ float2 sampler_noise(const SamplerArgs& p, int i, int draw) {
+  if (p.noise) return p.noise[(size_t)draw * p.n + i];
+  long long first;
+  const int b = sampler_utt(p, i, &first);
+  return sampler_noise_of(p, i, draw, b, first);
 }
 
 __global__ __launch_bounds__(256) void sampler_prior_kernel(SamplerArgs p) {
@@ -442,18 +457,19 @@ __global__ __launch_bounds__(256) void sampler_revdiff_kernel(SamplerArgs p) {
 
 constexpr int LANG_NBLK = 64;
 
-// pass 1: per-utterance partial sums of |score|^2 and |z|^2.  grid = (LANG_NBLK, B)
-__global__ __launch_bounds__(256) void sampler_langevin_norms_kernel(SamplerArgs p) {
+// pass 1: per-utterance partial sums of |score|^2 and |z|^2 over the `per` elements from `first` on.  grid = (LANG_NBLK, B).  Element i
+// of the utterance goes to workgroup (i / 256) % LANG_NBLK, thread i % 256, whatever the batch: a partial sum depends on the
+// element index inside the utterance only
+__device__ __forceinline__ void langevin_norms(const SamplerArgs& p, int b, long long first, int per) {
   __shared__ float s_a[4];
   __shared__ float s_b[4];
-  const int b = blockIdx.y;
   const int step = *p.step_ptr;
   const int draw = p.draw_base + step * p.draw_per_step;
   float g2 = 0.f, z2 = 0.f;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < p.per; i += LANG_NBLK * 256) {
-    const int e = b * p.per + i;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < per; i += LANG_NBLK * 256) {
+    const int e = (int)first + i;
     const float2 g = p.score[e];
-    const float2 z = sampler_noise(p, e, draw);
+    const float2 z = sampler_noise_of(p, e, draw, b, first);
     g2 += g.x * g.x + g.y * g.y;
     z2 += z.x * z.x + z.y * z.y;
   }
@@ -465,6 +481,17 @@ __global__ __launch_bounds__(256) void sampler_langevin_norms_kernel(SamplerArgs
     o[0] = (s_a[0] + s_a[1]) + (s_a[2] + s_a[3]);
     o[1] = (s_b[0] + s_b[1]) + (s_b[2] + s_b[3]);
   }
+}
+
+__global__ __launch_bounds__(256) void sampler_langevin_norms_kernel(SamplerArgs p) {
+  langevin_norms(p, blockIdx.y, (long long)blockIdx.y * p.per, p.per);
+}
+
+// ... of a uniform or ragged batch (per-utterance step size): utterance b = rag_off[b] .. rag_off[b + 1]
+__global__ __launch_bounds__(256) void sampler_langevin_norms_each_kernel(SamplerArgs p) {
+  const int b = blockIdx.y;
+  const long long first = p.rag_off ? p.rag_off[b] : (long long)b * p.per;
+  langevin_norms(p, b, first, p.rag_off ? (int)(p.rag_off[b + 1] - first) : p.per);
 }
 
 // pass 2 (one workgroup): grad_norm = mean_b ||score_b||, noise_norm = mean_b ||z_b||, step = 2 (snr noise_norm / grad_norm)^2
@@ -485,17 +512,43 @@ __global__ __launch_bounds__(64) void sampler_langevin_scalars_kernel(SamplerArg
   }
 }
 
+// pass 2, per utterance (one lane each): step_b = 2 (snr ||z_b|| / ||score_b||)^2 -> lang[2b], sqrt(2 step_b) -> lang[2b + 1]; the
+// operation sequence of the batch form at B = 1 (where its wave sum adds zeros and its mean divides by 1, both exact)
+__global__ __launch_bounds__(64) void sampler_langevin_scalars_each_kernel(SamplerArgs p) {
+  for (int b = threadIdx.x; b < p.B; b += 64) {
+    double g2 = 0.0, z2 = 0.0;
+    for (int k = 0; k < LANG_NBLK; ++k) { g2 += p.partial[((size_t)b * LANG_NBLK + k) * 2]; z2 += p.partial[((size_t)b * LANG_NBLK + k) * 2 + 1]; }
+    const float gn = sqrtf((float)g2), zn = sqrtf((float)z2);
+    const float r = p.snr * zn / gn;
+    const float stepsz = r * r * 2.f;
+    p.lang[2 * b] = stepsz;
+    p.lang[2 * b + 1] = sqrtf(stepsz * 2.f);
+  }
+}
+
 // pass 3: x_mean = x + step*score ; x = x_mean + z*sqrt(2 step)
-__global__ __launch_bounds__(256) void sampler_langevin_kernel(SamplerArgs p) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= p.n) return;
-  const int step = *p.step_ptr;
-  const float eps = p.lang[0], ns = p.lang[1];
-  const float2 z = sampler_noise(p, i, p.draw_base + step * p.draw_per_step);
+__device__ __forceinline__ void langevin_update(const SamplerArgs& p, int i, float eps, float ns, float2 z) {
   const float2 xv = p.x[i], g = p.score[i];
   const float2 xm = make_float2(xv.x + eps * g.x, xv.y + eps * g.y);
   p.x_mean[i] = xm;
   p.x[i] = make_float2(xm.x + z.x * ns, xm.y + z.y * ns);
+}
+
+__global__ __launch_bounds__(256) void sampler_langevin_kernel(SamplerArgs p) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.n) return;
+  const int step = *p.step_ptr;
+  langevin_update(p, i, p.lang[0], p.lang[1], sampler_noise(p, i, p.draw_base + step * p.draw_per_step));
+}
+
+// ... with the step size of the element's utterance: one lookup serves the noise counter and the step size
+__global__ __launch_bounds__(256) void sampler_langevin_each_kernel(SamplerArgs p) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.n) return;
+  const int step = *p.step_ptr;
+  long long first;
+  const int b = sampler_utt(p, i, &first);
+  langevin_update(p, i, p.lang[2 * b], p.lang[2 * b + 1], sampler_noise_of(p, i, p.draw_base + step * p.draw_per_step, b, first));
 }
 
 // Schroedinger-bridge samplers (reference sampling/__init__.py:145-249): every step is the weighted sum

@@ -98,7 +98,8 @@ def build_sampler(model: ScoreModel, Y: torch.Tensor, args, seed=None, streams=N
     if sde == "OUVESDE":
         if args.sampler_type == "pc":
             return model.get_pc_sampler("reverse_diffusion", args.corrector, Y, N=args.N, corrector_steps=args.corrector_steps,
-                                        snr=args.snr, seed=seed, streams=streams)
+                                        snr=args.snr, seed=seed, streams=streams,
+                                        corrector_scope=getattr(args, "corrector_scope", "batch"))
         if args.sampler_type == "ode":
             solver = getattr(args, "ode_solver", None)
             if solver is not None:      # the reference's adaptive RK45 sampler (rectangular batches only); 'native': as one library call
@@ -276,7 +277,9 @@ def enhance_files(model: ScoreModel, files: List[str], test_dir: str, enhanced_d
     together and inverted one by one with their own lengths.  A corpus of mixed lengths therefore runs in batches (64 frames =
     0.5 s at 16 kHz granularity) while every utterance keeps the arithmetic of its single-file run bit for bit.  With ``--seed``
     the noise of an utterance is a function of (seed, its index in the sorted file list): the enhanced files do not depend on
-    the batch size, the bucket an utterance landed in or the number of ranks.
+    the batch size, the bucket an utterance landed in or the number of ranks.  (One exception, the reference's own: ``--corrector
+    langevin`` at its default batch scope takes its step size from the batch-mean norms; ``--corrector_scope utterance`` takes every
+    file's own norms, as a one-file-at-a-time run does, and removes it.)
 
     Plumbing (none of it touches an utterance's arithmetic): the batches are planned from the file HEADERS; every file is read,
     resampled and peak-normalised once, on a pool of background threads that runs ahead of the GPU; waveforms of one length share
@@ -293,10 +296,12 @@ def enhance_files(model: ScoreModel, files: List[str], test_dir: str, enhanced_d
     if frames is None:
         frames = [padded_frames(probe_samples(p, target_sr), hop) for p in files]
     ragged = bool(getattr(args, "ragged", False))
-    if ragged and (model.sde.__class__.__name__ != "OUVESDE" or args.corrector == "langevin"):
+    if (ragged and model.sde.__class__.__name__ == "OUVESDE" and args.sampler_type == "pc" and args.corrector == "langevin"
+            and getattr(args, "corrector_scope", "batch") != "utterance"):
         import warnings
-        warnings.warn("--ragged needs an OUVE model and the 'ald' / 'none' corrector (the Langevin corrector couples the utterances of "
-                      "a batch; the Schroedinger-bridge sampler is not built for it): batching by padded length instead")
+        warnings.warn("--ragged does not combine with --corrector langevin at batch scope: its step size comes from the batch-mean norms, "
+                      "which couples the utterances of a batch: batching by padded length instead "
+                      "(--corrector_scope utterance takes every file's own norms, as in a one-file-at-a-time run, and keeps --ragged)")
         ragged = False
     ode_each = getattr(args, "ode_solver", None) == "native" and getattr(args, "ode_step_control", None) == "utterance"
     if ragged and args.sampler_type == "ode" and getattr(args, "ode_solver", None) is not None and not ode_each:
@@ -411,6 +416,10 @@ def main(argv=None) -> int:
                              "flattened state; 'utterance' = every file gets its own step control, as in a one-file-at-a-time run (an enhanced "
                              "file then does not depend on what shares its batch, and --ragged stays on)")
     parser.add_argument("--corrector", type=str, choices=("ald", "langevin", "none"), default="ald", help="Corrector class for the PC sampler.")
+    parser.add_argument("--corrector_scope", type=str, choices=("batch", "utterance"), default="batch",
+                        help="With --corrector langevin: 'batch' = one step size from the batch-mean norms of score and noise, as the reference "
+                             "computes it for a batch; 'utterance' = every file's own norms, as in a one-file-at-a-time run (an enhanced "
+                             "file then does not depend on what shares its batch, and --ragged stays on)")
     parser.add_argument("--corrector_steps", type=int, default=1, help="Number of corrector steps")
     parser.add_argument("--snr", type=float, default=0.5, help="SNR value for (annealed) Langevin dynmaics")
     parser.add_argument("--N", type=int, default=30, help="Number of reverse steps")
@@ -419,7 +428,8 @@ def main(argv=None) -> int:
     parser.add_argument("--batch_size", type=int, default=32, help="Utterances of equal padded length enhanced together")
     parser.add_argument("--seed", type=int, default=None, help="Base seed of the sampler noise (default: unseeded, like the reference)")
     parser.add_argument("--ragged", action="store_true", help="Batch files of different padded lengths together where the cost model says it pays "
-                                                              "(OUVE models, pc / ode samplers, ald / none correctors)")
+                                                              "(pc / ode / Schroedinger-bridge samplers; not with the batch-scope langevin corrector or the "
+                                                              "batch-controlled adaptive solver)")
     parser.add_argument("--balance", type=str, choices=("contiguous", "frames"), default="contiguous",
                         help="Files per rank under torchrun: the reference's contiguous split of the sorted list (default), or balanced by "
                              "padded frame count (longest-processing-time); the enhanced files are identical either way")

@@ -236,7 +236,9 @@ class ScoreModel(nn.Module):
         utterance; without explicit stream ids a chunk's utterances keep the ids they have in the whole batch (their position),
         so that chunked and unchunked runs of one seed draw the same noise."""
         kw = dict(kwargs)
-        if kw.get("noise") is not None:
+        if isinstance(kw.get("noise"), (list, tuple)):       # ragged batch: one [ndraws,1,F,T_b] tensor per utterance
+            kw["noise"] = list(kw["noise"][lo:hi])
+        elif kw.get("noise") is not None:
             kw["noise"] = kw["noise"][:, lo:hi].contiguous()
         kw["streams"] = list(range(lo, hi)) if kw.get("streams") is None else list(kw["streams"][lo:hi])
         return kw
@@ -258,6 +260,8 @@ class ScoreModel(nn.Module):
         return batched_sampling_fn
 
     def get_pc_sampler(self, predictor_name, corrector_name, y, N=None, minibatch=None, **kwargs):
+        """reference model.py:348-368.  Keyword arguments of sampling.get_pc_sampler pass through, among them ``corrector_scope``
+        ('utterance': the 'langevin' step size from each utterance's own norms) and, for a ragged list ``y``, list-valued ``noise``."""
         sde = self.sde.copy()
         sde.N = self.sde.N if N is None else N
         kwargs = {"eps": self.t_eps, **kwargs}
@@ -278,12 +282,14 @@ class ScoreModel(nn.Module):
         # (with minibatch the reference returns only the LAST chunk's samples, model.py:389; here all of them)
         return make(y, kwargs) if minibatch is None else self._chunked(make, y, minibatch, kwargs)
 
-    def get_sb_sampler(self, sde, y, sampler_type="ode", N=None, **kwargs):
-        """reference model.py:392-397 (the passed ``sde`` only supplies the default N; the model's own SDE is used)."""
+    def get_sb_sampler(self, sde, y, sampler_type="ode", N=None, minibatch=None, **kwargs):
+        """reference model.py:392-397 (the passed ``sde`` only supplies the default N; the model's own SDE is used).  ``y`` may be a
+        ragged list of spectrograms (library loop only); ``minibatch``: serial chunks as for the other samplers."""
         N = sde.N if N is None else N
         sde = self.sde.copy()
         sde.N = N if N is not None else sde.N
-        return sampling.get_sb_sampler(sde, self, y=y, sampler_type=sampler_type, **kwargs)
+        make = lambda yy, kw: sampling.get_sb_sampler(sde, self, y=yy, sampler_type=sampler_type, **kw)
+        return make(y, kwargs) if minibatch is None else self._chunked(make, y, minibatch, kwargs)
 
     # -- audio helpers (reference model.py:411-424) -----------------------------------------------------------
     def to_audio(self, spec, length=None):
@@ -338,25 +344,32 @@ class ScoreModel(nn.Module):
         return wave, nfe, (time.time() - t_begin) / (len(wave) / self.sr)
 
     def enhance_batch(self, y, N=30, corrector="ald", corrector_steps=1, snr=0.5, pad_mode="zero_pad", noise=None, seed=None,
-                      predictor="reverse_diffusion", sampler_type="pc", use_graph=True, streams=None):
+                      predictor="reverse_diffusion", sampler_type="pc", use_graph=True, streams=None, corrector_scope="batch"):
         """Batched form of enhancement.py:62-99: y float32 [B, L] (B utterances of equal length) -> enhanced float32 [B, L] on the
         model's device; or a LIST of 1-D waveforms of different lengths -> list of enhanced waveforms (one ragged batch, each
-        utterance bit-identical to its own single call with the same seed and stream id).  Not in the reference (which loops
-        files one by one)."""
+        utterance bit-identical to its own single call with the same seed and stream id; ``noise`` is then a list of
+        [ndraws,1,F,T_b] tensors, T_b the padded frame count).  A Schroedinger-bridge model runs its own sampler, as in
+        enhancement.build_sampler: 'ode' for ``sampler_type`` 'pc', else ``sampler_type``, with the model's own N.
+        ``corrector_scope='utterance'``: the 'langevin' corrector's step size per utterance (needed for a list).  Not in the
+        reference (which loops files one by one)."""
         dev = self._device()
+        sb = type(self.sde).__name__ == "SBVESDE"
+        if sb:
+            sb_sampler = lambda Y, nz: self.get_sb_sampler(sde=self.sde, y=Y, sampler_type="ode" if sampler_type == "pc" else sampler_type,
+                                                           noise=nz, seed=seed, use_graph=use_graph, streams=streams)
         if isinstance(y, (list, tuple)):
             # utterances of DIFFERENT lengths: one ragged batch (Context.set_frames) -- every utterance through its own STFT and
             # pad_spec, sampled together, inverted with its own length; returns a list of 1-D waveforms
-            if noise is not None:
-                raise ValueError("a list of waveforms (ragged batch) uses in-kernel noise only")
             ys = [w.reshape(1, -1).to(dev) for w in y]
             norms = [w.abs().max() for w in ys]
             Ys = [pad_spec(self._forward_transform(self._stft(w / n)).unsqueeze(1), mode=pad_mode)[0] for w, n in zip(ys, norms)]
-            if sampler_type == "pc":
-                sampler = self.get_pc_sampler(predictor, corrector, Ys, N=N, corrector_steps=corrector_steps, snr=snr, seed=seed,
-                                              use_graph=use_graph, streams=streams)
+            if sb:
+                sampler = sb_sampler(Ys, noise)
+            elif sampler_type == "pc":
+                sampler = self.get_pc_sampler(predictor, corrector, Ys, N=N, corrector_steps=corrector_steps, snr=snr, noise=noise, seed=seed,
+                                              use_graph=use_graph, streams=streams, corrector_scope=corrector_scope)
             elif sampler_type == "ode":
-                sampler = self.get_ode_sampler(Ys, N=N, seed=seed, use_graph=use_graph, streams=streams)
+                sampler = self.get_ode_sampler(Ys, N=N, noise=noise, seed=seed, use_graph=use_graph, streams=streams)
             else:
                 raise ValueError(f"Sampler type {sampler_type} not supported")
             samples, nfe = sampler()
@@ -366,9 +379,11 @@ class ScoreModel(nn.Module):
         norm = y.abs().amax(dim=1, keepdim=True)
         Y = self._forward_transform(self._stft(y / norm)).unsqueeze(1)
         Y = pad_spec(Y, mode=pad_mode)
-        if sampler_type == "pc":
+        if sb:
+            sampler = sb_sampler(Y, noise)
+        elif sampler_type == "pc":
             sampler = self.get_pc_sampler(predictor, corrector, Y, N=N, corrector_steps=corrector_steps, snr=snr, noise=noise,
-                                          seed=seed, use_graph=use_graph, streams=streams)
+                                          seed=seed, use_graph=use_graph, streams=streams, corrector_scope=corrector_scope)
         elif sampler_type == "ode":
             sampler = self.get_ode_sampler(Y, N=N, noise=noise, seed=seed, use_graph=use_graph, streams=streams)
         else:

@@ -38,20 +38,27 @@ def _native_engine(score_fn, y):
 def _require_native_for_ragged(ctx, y):
     """A list of spectrograms of different lengths (ragged batch, Context.set_frames) only runs on the native samplers."""
     if ctx is None and isinstance(y, (list, tuple)):
-        raise TypeError("a list of spectrograms (ragged batch) needs the native HIP sampler: OUVESDE, 'reverse_diffusion'/'none' "
-                        "predictor, 'ald'/'none' corrector, no force_python_loop")
+        raise TypeError("a list of spectrograms (ragged batch) needs the native HIP sampler: OUVESDE with a 'reverse_diffusion'/'none' "
+                        "predictor and an 'ald'/'none'/'langevin' (corrector_scope='utterance') corrector, or SBVESDE with "
+                        "get_sb_sampler; no force_python_loop")
 
 
 def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=True, eps=3e-2, snr=0.1, corrector_steps=1,
                    probability_flow: bool = False, intermediate=False, noise: Optional[torch.Tensor] = None,
-                   seed: Optional[int] = None, use_graph: bool = True, force_python_loop: bool = False, streams=None, **kwargs):
+                   seed: Optional[int] = None, use_graph: bool = True, force_python_loop: bool = False, streams=None,
+                   corrector_scope: str = "batch", **kwargs):
     """Predictor-corrector sampler (reference sampling/__init__.py:26-70).
 
     Extra keyword arguments of this implementation: ``noise`` (complex64 [ndraws,B,1,F,T] replayed standard-normal
     draws in the reference's call order, for bit-comparable runs), ``seed`` (Philox seed when ``noise`` is None;
     default: drawn from torch's global RNG), ``streams`` (one integer per utterance naming its noise stream: the draws of an
     utterance then depend on (seed, stream) only, not on its batch slot; default: the slot), ``use_graph``,
-    ``force_python_loop``."""
+    ``force_python_loop``, ``corrector_scope`` ('batch': the 'langevin' corrector takes its step size from the batch-mean norms, as
+    the reference does; 'utterance': from each utterance's own norms, so an utterance gets what the reference's one-file-at-a-time
+    loop gives it and ``y`` may be a ragged list; accepted with every corrector, it only matters for 'langevin').  With a ragged
+    list ``y``, ``noise`` is a list of [ndraws,1,F,T_b] tensors."""
+    if corrector_scope not in ("batch", "utterance"):
+        raise ValueError(f"corrector_scope must be 'batch' or 'utterance', got {corrector_scope!r}")
     predictor_cls = PredictorRegistry.get_by_name(predictor_name)   # ValueError for unknown names, like the reference
     corrector_cls = CorrectorRegistry.get_by_name(corrector_name)
 
@@ -71,12 +78,13 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=Tru
                 out, nfe = ctx.pc_sample(y, table, theta=float(sde.theta), std1=std1, corrector=corrector_name,
                                          corrector_steps=corrector_steps, predictor=predictor_name,
                                          probability_flow=False, denoise=denoise, noise=noise, seed=s, use_graph=use_graph,
-                                         affine=affine, snr=snr, streams=streams)
+                                         affine=affine, snr=snr, streams=streams, corrector_scope=corrector_scope)
             return out, nfe
         return native_pc_sampler
 
     predictor = predictor_cls(sde, score_fn, probability_flow=probability_flow)
-    corrector = corrector_cls(sde, score_fn, snr=snr, n_steps=corrector_steps)
+    scope = dict(scope=corrector_scope) if corrector_name == "langevin" else {}
+    corrector = corrector_cls(sde, score_fn, snr=snr, n_steps=corrector_steps, **scope)
 
     def pc_sampler():
         with torch.no_grad():
@@ -286,10 +294,13 @@ def get_sb_sampler(sde, model, y, eps=1e-4, n_steps=50, sampler_type="ode", nois
                    seed: Optional[int] = None, use_graph: bool = True, force_python_loop: bool = False, streams=None, **kwargs):
     """Schroedinger-bridge samplers (reference sampling/__init__.py:145-249): 'ode' (deterministic) and 'sde'.  With a
     ScoreModel on a HIP backbone the N-step loop runs in the library (sgmse_sb_sample); otherwise the reference-style
-    Python loop below.  Returns a zero-argument callable -> (sample, n_steps) like the reference."""
+    Python loop below.  Returns a zero-argument callable -> (sample, n_steps) like the reference.  The library loop also takes a
+    ragged list of [F,T_b] / [1,F,T_b] spectrograms (and then ``noise`` as a list of [ndraws,1,F,T_b]) and returns a list of
+    [1,F,T_b], every utterance bit-identical to its own single-utterance call; the Python loop refuses a list."""
     if sampler_type not in ("ode", "sde"):
         raise ValueError("Invalid type. Choose 'ode' or 'sde'.")
     ctx = None if force_python_loop else (_native_engine(model, y) if isinstance(sde, SBVESDE) else None)
+    _require_native_for_ragged(ctx, y)
     if ctx is not None:
         table = sde.sb_step_table(eps, sampler_type, sde.N)
         affine = model.score_affine(table["t"])
@@ -297,7 +308,8 @@ def get_sb_sampler(sde, model, y, eps=1e-4, n_steps=50, sampler_type="ode", nois
         def native_sb_sampler():
             s = seed if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
             with torch.no_grad():
-                out, _ = ctx.sb_sample(y[:, [0], :, :].contiguous(), table, stochastic=(sampler_type == "sde"), noise=noise, seed=s,
+                y0 = list(y) if isinstance(y, (list, tuple)) else y[:, [0], :, :].contiguous()
+                out, _ = ctx.sb_sample(y0, table, stochastic=(sampler_type == "sde"), noise=noise, seed=s,
                                        affine=affine, use_graph=use_graph, streams=streams)
             return out, n_steps
         return native_sb_sampler

@@ -11,7 +11,7 @@ Both Langevin variants are the same iteration
 
 and differ only in the step size eps, so the loop lives once in ``_LangevinLoop`` and a variant supplies ``_eps``:
 'ald' anneals with the SDE's marginal standard deviation (one eps per utterance), 'langevin' balances the batch-mean
-norms of noise and score (one eps for the whole batch).
+norms of noise and score (one eps for the whole batch; with scope='utterance' each utterance's own norms, one eps each).
 """
 import abc
 
@@ -60,11 +60,20 @@ class _LangevinLoop(Corrector):
 @CorrectorRegistry.register(name="langevin")
 class LangevinCorrector(_LangevinLoop):
     """eps = 2 (snr * mean_b ||z_b|| / mean_b ||score_b||)^2: the only place of the path where utterances of a batch
-    interact (correctors.py:50-52)."""
+    interact (correctors.py:50-52).  ``scope='utterance'`` leaves the two means out: eps_b = 2 (snr * ||z_b|| / ||score_b||)^2, what
+    utterance b gets in a batch of its own (the reference's one-file-at-a-time enhancement loop)."""
+
+    def __init__(self, sde, score_fn, snr, n_steps, scope="batch"):
+        super().__init__(sde, score_fn, snr, n_steps)
+        if scope not in ("batch", "utterance"):
+            raise ValueError(f"scope must be 'batch' or 'utterance', got {scope!r}")
+        self.scope = scope
 
     def _eps(self, x, y, t, score, z):
-        flat_norm = lambda v: torch.norm(v.reshape(v.shape[0], -1), dim=-1).mean()
-        return ((self.snr * flat_norm(z) / flat_norm(score)) ** 2 * 2).unsqueeze(0)
+        flat_norm = lambda v: torch.norm(v.reshape(v.shape[0], -1), dim=-1)
+        if self.scope == "utterance":
+            return (self.snr * flat_norm(z) / flat_norm(score)) ** 2 * 2
+        return ((self.snr * flat_norm(z).mean() / flat_norm(score).mean()) ** 2 * 2).unsqueeze(0)
 
 
 @CorrectorRegistry.register(name="ald")
