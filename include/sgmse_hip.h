@@ -178,6 +178,25 @@ int sgmse_istft(sgmse_ctx* ctx, const void* spec, const float* window, float* ou
 int sgmse_spec_fwd(sgmse_ctx* ctx, const void* in, void* out, long long n, int transform_type, float factor, float exponent);
 int sgmse_spec_back(sgmse_ctx* ctx, const void* in, void* out, long long n, int transform_type, float factor, float exponent);
 
+/* -- windows of a long spectrogram (not in the reference, which enhances a recording as one spectrogram) ----------------------
+ * A plan is n windows, window j = frames [start[j], start[j] + frames[j]) of a spectrogram of K frames; start and frames are HOST
+ * arrays of length n.  Both calls return SGMSE_EINVAL (message in sgmse_last_error) unless the starts are strictly increasing, every
+ * window lies inside [0, K), the windows cover [0, K) without a gap and no frame lies under three windows (nor may a window end
+ * inside its predecessor: a frame's one or two windows are then always neighbours).
+ * `windows` is PACKED: window after window, complex64 [F][frames[j]] each -- what a ragged context (sgmse_set_frames with these
+ * frame counts) takes for Y and returns for out.  transform_type / factor / exponent: as for sgmse_spec_fwd.
+ * split: windows[j][f][t] = spec_fwd(spec[f][start[j] + t]) for the untransformed spec complex64 [F][K]: a gather, bit-identical to
+ *    slicing sgmse_spec_fwd's output. */
+int sgmse_spec_split(sgmse_ctx* ctx, const void* spec, void* windows, int F, int K, const int* start, const int* frames, int n,
+                     int transform_type, float factor, float exponent);
+/* merge: spec[f][k] (complex64 [F][K], back-transformed) from the transformed-domain windows.  A frame under one window:
+ *    spec_back of its element, bit-identical to sgmse_spec_back.  A frame under windows j and j + 1, whose overlap
+ *    [start[j+1], start[j] + frames[j]) has O_j frames: with a = spec_back(window j's element), b = spec_back(window j+1's) and
+ *    w = ((float)(k - start[j+1]) + 0.5f) / (float)O_j, each real component is fmaf(w, b - a, a): a linear cross-fade of the two
+ *    back-transformed signals, w running from 0.5 / O_j to 1 - 0.5 / O_j.  One thread per output element, no atomics. */
+int sgmse_spec_merge(sgmse_ctx* ctx, const void* windows, void* spec, int F, int K, const int* start, const int* frames, int n,
+                     int transform_type, float factor, float exponent);
+
 /* -- upfirdn2d(input, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1)
  *    (op/upfirdn2d.cpp:12-23, op/upfirdn2d_kernel.cu:209-369).  input fp32 [BC][H][W], kernel fp32 [kh][kw],
  *    out fp32 [BC][(H*up_y+pad_y0+pad_y1-kh)/down_y+1][(W*up_x+pad_x0+pad_x1-kw)/down_x+1]. */

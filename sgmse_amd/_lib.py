@@ -74,6 +74,8 @@ _SIGS = {
     "sgmse_istft": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "sgmse_spec_fwd": (_I, [_P, _P, _P, _LL, _I, _F, _F]),
     "sgmse_spec_back": (_I, [_P, _P, _P, _LL, _I, _F, _F]),
+    "sgmse_spec_split": (_I, [_P, _P, _P, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _F, _F]),
+    "sgmse_spec_merge": (_I, [_P, _P, _P, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, _I, _F, _F]),
     "sgmse_upfirdn2d": (_I, [_P, _P, _P, _P] + [_I] * 13),
     "sgmse_upfirdn2d_dtype": (_I, [_P, _I, _P, _P, _P] + [_I] * 13),
     "sgmse_op_conv2d": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _I, _P, _I]),
@@ -636,6 +638,35 @@ class Context:
         arr = (_I * max(len(frames), 1))(*frames)
         self.check(self.lib.sgmse_set_frames(self.h, arr if frames else None, len(frames)))
         self._frames = frames
+
+    def _window_call(self, fn, src, dst, F_: int, K: int, starts, frames, transform_type: int, factor: float, exponent: float) -> None:
+        starts, frames = [int(v) for v in starts], [int(v) for v in frames]
+        if len(starts) != len(frames) or not starts:
+            raise ValueError(f"a window plan is two lists of one length >= 1, got {len(starts)} starts and {len(frames)} frame counts")
+        n = len(starts)
+        self.use_current_stream()
+        self.check(fn(self.h, src.data_ptr(), dst.data_ptr(), F_, K, (_I * n)(*starts), (_I * n)(*frames), n, int(transform_type),
+                      float(factor), float(exponent)))
+
+    def spec_split(self, spec: torch.Tensor, starts, frames, transform_type: int, factor: float, exponent: float) -> torch.Tensor:
+        """sgmse_spec_split: spec complex64 [F,K] (untransformed) -> the packed windows (flat complex64, window after window, [F,T_i]
+        each, spec_fwd applied).  ValueError for a plan the library refuses."""
+        spec = check_tensor(spec, "spec", torch.complex64, self.device)
+        if spec.dim() != 2:
+            raise ValueError(f"expected spec of shape [F,K], got {tuple(spec.shape)}")
+        F_, K = spec.shape
+        out = torch.empty(F_ * sum(max(int(v), 0) for v in frames), dtype=torch.complex64, device=self.device)
+        self._window_call(self.lib.sgmse_spec_split, spec, out, F_, K, starts, frames, transform_type, factor, exponent)
+        return out
+
+    def spec_merge(self, windows: torch.Tensor, F_: int, K: int, starts, frames, transform_type: int, factor: float, exponent: float) -> torch.Tensor:
+        """sgmse_spec_merge: the packed windows (transformed domain) -> complex64 [F,K], back-transformed, overlaps cross-faded."""
+        windows = check_tensor(windows, "windows", torch.complex64, self.device)
+        if windows.numel() != F_ * sum(int(v) for v in frames):
+            raise ValueError(f"the packed windows must hold F * sum(frames) = {F_ * sum(int(v) for v in frames)} elements, got {windows.numel()}")
+        out = torch.empty((F_, K), dtype=torch.complex64, device=self.device)
+        self._window_call(self.lib.sgmse_spec_merge, windows, out, F_, K, starts, frames, transform_type, factor, exponent)
+        return out
 
     def forward_ragged(self, xys, t: torch.Tensor):
         """NCSNpp.forward on utterances of different lengths in ONE batch: xys = list of complex64 [2,F,T_b]; returns the list of

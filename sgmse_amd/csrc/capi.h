@@ -41,6 +41,23 @@ static int sg_ode_run(sgmse_ctx* ctx, const void* Y, void* out, int B, int F, in
     if (nfe) *nfe = e.last_nfe();
   });
 }
+
+// sgmse_spec_split / sgmse_spec_merge: what is wrong with a window plan over K frames, or nullptr.  Besides the four conditions of the
+// header, no window may end at or behind its successor's end (the cross-fade is defined between neighbours that each reach past the other).
+static const char* sg_check_windows(int K, const int* start, const int* frames, int n) {
+  long long total = 0;
+  for (int j = 0; j < n; ++j) {
+    if (frames[j] < 1 || start[j] < 0 || (long long)start[j] + frames[j] > K) return "a window does not lie inside [0, K)";
+    if (j > 0 && start[j] <= start[j - 1]) return "window starts must be strictly increasing";
+    if (j == 0 ? start[0] != 0 : start[j] > start[j - 1] + frames[j - 1]) return "the windows leave a gap: they must cover [0, K)";
+    if (j > 1 && start[j] < start[j - 2] + frames[j - 2]) return "a frame lies under three windows";
+    if (j > 0 && start[j] + frames[j] <= start[j - 1] + frames[j - 1]) return "a window ends inside its predecessor: ends must be strictly increasing";
+    total += frames[j];
+  }
+  if (start[n - 1] + frames[n - 1] != K) return "the windows leave a gap: they must cover [0, K)";
+  if (total > 0x7fffffffLL) return "the windows hold more than 2^31 - 1 frames";
+  return nullptr;
+}
 }  // namespace
 
 extern "C" {
@@ -170,6 +187,22 @@ int sgmse_spec_fwd(sgmse_ctx* ctx, const void* in, void* out, long long n, int t
 int sgmse_spec_back(sgmse_ctx* ctx, const void* in, void* out, long long n, int type, float factor, float exponent) {
   SG_ARG(ctx, in && out && n > 0 && type >= 0 && type <= 2, "bad arguments");
   return sg_guard(ctx, [&](sgmse::Engine& e) { e.op_spec_xform((const float2*)in, (float2*)out, (size_t)n, type, factor, exponent, 1); });
+}
+
+int sgmse_spec_split(sgmse_ctx* ctx, const void* spec, void* windows, int F, int K, const int* start, const int* frames, int n, int type,
+                     float factor, float exponent) {
+  SG_ARG(ctx, spec && windows && start && frames && F > 0 && K > 0 && n > 0 && type >= 0 && type <= 2, "bad arguments");
+  const char* bad = sg_check_windows(K, start, frames, n);
+  SG_ARG(ctx, bad == nullptr, bad);
+  return sg_guard(ctx, [&](sgmse::Engine& e) { e.op_spec_split((const float2*)spec, (float2*)windows, F, K, start, frames, n, type, factor, exponent); });
+}
+
+int sgmse_spec_merge(sgmse_ctx* ctx, const void* windows, void* spec, int F, int K, const int* start, const int* frames, int n, int type,
+                     float factor, float exponent) {
+  SG_ARG(ctx, spec && windows && start && frames && F > 0 && K > 0 && n > 0 && type >= 0 && type <= 2, "bad arguments");
+  const char* bad = sg_check_windows(K, start, frames, n);
+  SG_ARG(ctx, bad == nullptr, bad);
+  return sg_guard(ctx, [&](sgmse::Engine& e) { e.op_spec_merge((const float2*)windows, (float2*)spec, F, K, start, frames, n, type, factor, exponent); });
 }
 
 int sgmse_upfirdn2d(sgmse_ctx* ctx, const float* input, const float* kernel, float* out, int BC, int H, int W, int kh, int kw,

@@ -7,6 +7,7 @@
 // 130-135,188-229 (OUVE discretisation).  Nothing here is numerics except index bookkeeping: all arithmetic is in
 // the kernels.
 #pragma once
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -916,6 +917,36 @@ class Engine {
   void op_spec_xform(const float2* in, float2* out, size_t n, int type, float factor, float exponent, int inverse) {
     SpecXformArgs a{in, out, n, type, factor, exponent, inverse};
     DRT_LAUNCH(spec_xform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), stream_, a);
+    check_launch();
+  }
+
+  // Windows of a long spectrogram (kernels_stft.h: spec_split_kernel / spec_merge_kernel).  The plan -- checked by the caller
+  // (capi.h: sg_check_windows) -- goes to the device as start | frames | col0 through the staging buffer.
+  const int* upload_windows(const int* start, const int* frames, int n) {
+    const size_t nb = (size_t)3 * n * sizeof(int);
+    grow(win_tab_, nb);
+    int* h = reinterpret_cast<int*>(stage_.acquire(nb));
+    int col = 0;
+    for (int j = 0; j < n; ++j) { h[j] = start[j]; h[n + j] = frames[j]; h[2 * n + j] = col; col += frames[j]; }
+    SG_CHECK(drt::memcpy_h2d(win_tab_, h, nb, stream_));
+    stage_.commit(stream_);
+    return win_tab_.get();
+  }
+
+  void op_spec_split(const float2* spec, float2* windows, int F, int K, const int* start, const int* frames, int n, int type, float factor,
+                     float exponent) {
+    SG_REQUIRE(n <= 65535 && F <= 65535, "spec_split: more than 65535 windows or rows");
+    SpecWinArgs a{spec, windows, upload_windows(start, frames, n), F, K, n, type, factor, exponent};
+    const int tmax = *std::max_element(frames, frames + n);
+    DRT_LAUNCH(spec_split_kernel, dim3((tmax + 255) / 256, F, n), dim3(256), stream_, a);
+    check_launch();
+  }
+
+  void op_spec_merge(const float2* windows, float2* spec, int F, int K, const int* start, const int* frames, int n, int type, float factor,
+                     float exponent) {
+    SG_REQUIRE(F <= 65535, "spec_merge: more than 65535 rows");
+    SpecWinArgs a{windows, spec, upload_windows(start, frames, n), F, K, n, type, factor, exponent};
+    DRT_LAUNCH(spec_merge_kernel, dim3((K + 255) / 256, F), dim3(256), stream_, a);
     check_launch();
   }
 
@@ -2004,6 +2035,7 @@ class Engine {
   static constexpr int kMaxStreams = 4096;
   std::vector<unsigned long long> streams_next_;
   DevArray<unsigned long long> seed_dev_;
+  DevArray<int> win_tab_;             // window plan of the last spec_split / spec_merge
   int graph_captures_ = 0;
 
   int device_;

@@ -96,39 +96,84 @@ __global__ __launch_bounds__(256) void istft_kernel(IstftArgs p) {
 // spec_fwd / spec_back, transform_type in {exponent=0, log=1, none=2}; element-wise on complex data.
 struct SpecXformArgs { const float2* in; float2* out; size_t n; int type; float factor, exponent; int inverse; };
 
-__global__ __launch_bounds__(256) void spec_xform_kernel(SpecXformArgs p) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= p.n) return;
-  float2 v = p.in[i];
-  if (!p.inverse) {
-    if (p.type == 0) {
-      if (p.exponent != 1.f) {
+// The arithmetic of one element (reference data_module.py:162-188); the stand-alone transform and the window kernels below share it.
+__device__ __forceinline__ float2 spec_xform(float2 v, int type, float factor, float exponent, int inverse) {
+  if (!inverse) {
+    if (type == 0) {
+      if (exponent != 1.f) {
         const float mag = sqrtf(v.x * v.x + v.y * v.y);
-        const float g = mag > 0.f ? powf(mag, p.exponent) / mag : 0.f;
+        const float g = mag > 0.f ? powf(mag, exponent) / mag : 0.f;
         v.x *= g; v.y *= g;
       }
-      v.x *= p.factor; v.y *= p.factor;
-    } else if (p.type == 1) {
+      v.x *= factor; v.y *= factor;
+    } else if (type == 1) {
       const float mag = sqrtf(v.x * v.x + v.y * v.y);
       const float g = mag > 0.f ? log1pf(mag) / mag : 0.f;
-      v.x *= g * p.factor; v.y *= g * p.factor;
+      v.x *= g * factor; v.y *= g * factor;
     }
   } else {
-    if (p.type == 0) {
-      v.x /= p.factor; v.y /= p.factor;
-      if (p.exponent != 1.f) {
+    if (type == 0) {
+      v.x /= factor; v.y /= factor;
+      if (exponent != 1.f) {
         const float mag = sqrtf(v.x * v.x + v.y * v.y);
-        const float g = mag > 0.f ? powf(mag, 1.0f / p.exponent) / mag : 0.f;
+        const float g = mag > 0.f ? powf(mag, 1.0f / exponent) / mag : 0.f;
         v.x *= g; v.y *= g;
       }
-    } else if (p.type == 1) {
-      v.x /= p.factor; v.y /= p.factor;
+    } else if (type == 1) {
+      v.x /= factor; v.y /= factor;
       const float mag = sqrtf(v.x * v.x + v.y * v.y);
       const float g = mag > 0.f ? (expf(mag) - 1.f) / mag : 0.f;
       v.x *= g; v.y *= g;
     }
   }
-  p.out[i] = v;
+  return v;
+}
+
+__global__ __launch_bounds__(256) void spec_xform_kernel(SpecXformArgs p) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= p.n) return;
+  p.out[i] = spec_xform(p.in[i], p.type, p.factor, p.exponent, p.inverse);
+}
+
+// Windows of a long spectrogram (sgmse_spec_split / sgmse_spec_merge).  spec is [F][K]; window j holds the frames
+// [start[j], start[j] + frames[j]) as its own [F][frames[j]] block, the blocks packed one after the other: block j begins at element
+// F * col0[j], col0[j] = frames[0] + ... + frames[j-1] (the layout of a ragged batch).  tab = start[n] | frames[n] | col0[n].  The host
+// has checked the plan: starts and ends strictly increasing, no gap, every frame under one or two windows.  Frames are fastest in
+// both layouts and an element is 8 bytes, so a wave reads and writes consecutive 8-byte words.
+struct SpecWinArgs { const float2* src; float2* dst; const int* tab; int F, K, n, type; float factor, exponent; };
+
+// grid = (ceil(max_j frames[j] / 256), F, n): thread t of window j, row f.  A gather: windows[j][f][t] = spec_fwd(spec[f][start[j] + t]).
+__global__ __launch_bounds__(256) void spec_split_kernel(SpecWinArgs p) {
+  const int t = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y, j = blockIdx.z;
+  const int Tj = p.tab[p.n + j];
+  if (t >= Tj) return;
+  const float2 v = p.src[(size_t)f * p.K + p.tab[j] + t];
+  p.dst[(size_t)p.F * p.tab[2 * p.n + j] + (size_t)f * Tj + t] = spec_xform(v, p.type, p.factor, p.exponent, 0);
+}
+
+// grid = (ceil(K / 256), F): one thread per output element (f, k), no atomics.  j = the last window that starts at or before k covers
+// k; window j - 1 covers it too when it ends behind k, and the two are cross-faded linearly over their overlap AFTER spec_back.
+__global__ __launch_bounds__(256) void spec_merge_kernel(SpecWinArgs p) {
+  const int k = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+  if (k >= p.K) return;
+  const int* start = p.tab; const int* frames = p.tab + p.n; const int* col0 = p.tab + 2 * p.n;
+  int lo = 0, hi = p.n - 1;                  // start[0] = 0 <= k
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (start[mid] <= k) lo = mid; else hi = mid - 1;
+  }
+  const int j = lo, sj = start[j], Tj = frames[j];
+  float2 b = spec_xform(p.src[(size_t)p.F * col0[j] + (size_t)f * Tj + (k - sj)], p.type, p.factor, p.exponent, 1);
+  if (j > 0) {
+    const int si = start[j - 1], Ti = frames[j - 1], ov = si + Ti - sj;      // overlap [sj, si + Ti)
+    if (k < si + Ti) {
+      const float2 a = spec_xform(p.src[(size_t)p.F * col0[j - 1] + (size_t)f * Ti + (k - si)], p.type, p.factor, p.exponent, 1);
+      const float w = ((float)(k - sj) + 0.5f) / (float)ov;
+      b.x = fmaf(w, b.x - a.x, a.x);
+      b.y = fmaf(w, b.y - a.y, a.y);
+    }
+  }
+  p.dst[(size_t)f * p.K + k] = b;
 }
 
 }  // namespace sgmse

@@ -1,7 +1,7 @@
 """Signal front-end of the enhancement path (reference sgmse/data_module.py:13-19,103-236, front-end methods only).
 
 ``SpecsDataModule`` keeps the reference's constructor signature and the methods the inference path uses
-(``stft``, ``istft``, ``spec_fwd``, ``spec_back``, ``stft_kwargs``, ``istft_kwargs``, ``_get_window``); every transform
+(``stft``, ``istft``, ``spec_fwd``, ``spec_back``, ``split_windows``, ``merge_windows``, ``stft_kwargs``, ``istft_kwargs``, ``_get_window``); every transform
 runs in the HIP library.  Dataset / dataloader functionality (training) is out of scope and raises.  The class is
 importable under this name because Lightning checkpoints pickle it inside ``hyper_parameters`` (model.py:87-88)."""
 import torch
@@ -64,6 +64,15 @@ class SpecsDataModule:
         if self.transform_type == "none":
             return spec
         return ops.spec_transform(spec, self.transform_type, self.spec_factor, self.spec_abs_exponent, inverse=True)
+
+    def split_windows(self, spec, starts, frames):
+        """spec_fwd of an untransformed spectrogram [F,K], cut into the windows of a plan (util/windows.plan_windows): a list of
+        [F,T_i] views of one packed buffer.  Not in the reference."""
+        return ops.spec_split(spec, starts, frames, self.transform_type, self.spec_factor, self.spec_abs_exponent)
+
+    def merge_windows(self, windows, starts, frames, K):
+        """spec_back of the windows, joined to [F,K] with a linear cross-fade over every overlap (ops.spec_merge)."""
+        return ops.spec_merge(windows, starts, frames, K, self.transform_type, self.spec_factor, self.spec_abs_exponent)
 
     @property
     def stft_kwargs(self):

@@ -20,6 +20,11 @@ Differences from the reference script, none of them in the arithmetic of one utt
   reads the checkpoint and the weights reach the other ranks in one RCCL broadcast; there is no collective on the data path;
 * every file is read / resampled once on background threads ahead of the GPU, and the inverse transform + file writes of a
   batch overlap the sampling of the next one;
+* with ``--window_frames W`` (default 0: off, nothing changes) a file whose spectrogram has more than W frames is enhanced in
+  windows of at most W frames that overlap by ``--window_overlap`` frames and are cross-faded (``ScoreModel.enhance_long``): its
+  memory no longer grows with its length and the network sees the context length it was trained on.  THIS DEPARTS FROM THE
+  REFERENCE, which has no such mode and enhances every recording as one spectrogram: a windowed file is not what the reference
+  computes for it.  Files of at most W frames stay in the batches above, unchanged;
 * audio I/O uses ``soundfile`` when it is installed; otherwise ``scipy.io.wavfile`` for wav and the package's own decoder
   (util/flac.py) for flac input; resampling to the
   model's rate uses ``scipy.signal.resample_poly`` (the reference: ``librosa.resample``).
@@ -119,13 +124,19 @@ def build_sampler(model: ScoreModel, Y: torch.Tensor, args, seed=None, streams=N
     raise ValueError(f"SDE {sde} not supported")
 
 
-def _load_normalised(path: str, target_sr: int) -> Tuple[torch.Tensor, float]:
-    """File -> peak-normalised mono waveform at the model's rate and its peak (enhancement.py:62-72)."""
+def _load_wave(path: str, target_sr: int) -> np.ndarray:
+    """File -> mono float32 waveform at the model's rate."""
     y, sr = read_audio(path)
     if sr != target_sr:
         from scipy.signal import resample_poly
         g = gcd(sr, target_sr)
         y = resample_poly(y, target_sr // g, sr // g).astype(np.float32)
+    return y
+
+
+def _load_normalised(path: str, target_sr: int) -> Tuple[torch.Tensor, float]:
+    """File -> peak-normalised mono waveform at the model's rate and its peak (enhancement.py:62-72)."""
+    y = _load_wave(path, target_sr)
     peak = float(np.abs(y).max()) or 1.0
     return torch.from_numpy(y / peak), peak
 
@@ -269,6 +280,34 @@ class _Writer:
         return self.done
 
 
+def long_recording_args(model: ScoreModel, args, pad_mode: str) -> dict:
+    """The sampler arguments of ``ScoreModel.enhance_long`` that make its sampler calls those of ``build_sampler`` for ``args``."""
+    kw = dict(sampler_type=args.sampler_type, corrector=args.corrector, corrector_steps=args.corrector_steps, snr=args.snr, N=args.N,
+              corrector_scope=getattr(args, "corrector_scope", "batch"), pad_mode=pad_mode)
+    solver = getattr(args, "ode_solver", None)
+    if args.sampler_type == "ode" and solver is not None and model.sde.__class__.__name__ == "OUVESDE":
+        kw.update(adaptive=True, denoise=False, solver=solver)
+        if solver == "native" and getattr(args, "ode_step_control", None) == "utterance":
+            kw["step_control"] = "utterance"
+    return kw
+
+
+def enhance_long_files(model: ScoreModel, files: List[str], test_dir: str, enhanced_dir: str, args, gidx: List[int]) -> int:
+    """The files of ``--window_frames`` that do not fit one window, one after the other through ``ScoreModel.enhance_long`` with the
+    file's global index as its noise-stream id (window i of file g draws from stream g + (i << 32)): the written file is a function
+    of (seed, g) and does not depend on ``--batch_size``, which here is the number of windows per sampler call."""
+    target_sr, pad_mode = model_audio_settings(model)
+    kw = long_recording_args(model, args, pad_mode)
+    for path, g in zip(files, gidx):
+        y = torch.from_numpy(_load_wave(path, target_sr))
+        x, _ = model.enhance_long(y, window_frames=args.window_frames, overlap_frames=args.window_overlap, batch_size=args.batch_size,
+                                  seed=args.seed, stream=g, **kw)
+        name = path.replace(test_dir, "")
+        name = name[1:] if name.startswith("/") else name
+        write_audio(join(enhanced_dir, name), x.cpu().numpy(), target_sr)
+    return len(files)
+
+
 def enhance_files(model: ScoreModel, files: List[str], test_dir: str, enhanced_dir: str, args, device, first_index: int = 0,
                   indices=None, frames=None) -> int:
     """Enhance ``files`` in batches.  What has to agree inside a (uniform) batch is the PADDED spectrogram shape, not the waveform
@@ -295,6 +334,18 @@ def enhance_files(model: ScoreModel, files: List[str], test_dir: str, enhanced_d
     gidx = list(indices) if indices is not None else [first_index + k for k in range(n)]
     if frames is None:
         frames = [padded_frames(probe_samples(p, target_sr), hop) for p in files]
+    # --window_frames: recordings longer than one window leave the batch plan and run window by window (enhance_long_files)
+    W = int(getattr(args, "window_frames", 0) or 0)
+    n_long = 0
+    if W > 0:
+        from .util.windows import plan_windows
+        plan_windows(1, W, args.window_overlap)                # the two switches are checked before any file is touched
+        long_ = [k for k in range(n) if frames[k] > W]                    # W % 64 == 0: padded frames > W <=> frames > W
+        if long_:
+            n_long = enhance_long_files(model, [files[k] for k in long_], test_dir, enhanced_dir, args, [gidx[k] for k in long_])
+            keep = [k for k in range(n) if frames[k] <= W]
+            files, gidx, frames = [files[k] for k in keep], [gidx[k] for k in keep], [frames[k] for k in keep]
+            n = len(files)
     ragged = bool(getattr(args, "ragged", False))
     if (ragged and model.sde.__class__.__name__ == "OUVESDE" and args.sampler_type == "pc" and args.corrector == "langevin"
             and getattr(args, "corrector_scope", "batch") != "utterance"):
@@ -373,7 +424,7 @@ def enhance_files(model: ScoreModel, files: List[str], test_dir: str, enhanced_d
         writer.close(reraise=False)
         raise
     pool.shutdown(wait=False, cancel_futures=True)
-    return writer.close()
+    return writer.close() + n_long
 
 
 def load_model(ckpt: str, device, rank: int, world: int) -> ScoreModel:
@@ -430,6 +481,14 @@ def main(argv=None) -> int:
     parser.add_argument("--ragged", action="store_true", help="Batch files of different padded lengths together where the cost model says it pays "
                                                               "(pc / ode / Schroedinger-bridge samplers; not with the batch-scope langevin corrector or the "
                                                               "batch-controlled adaptive solver)")
+    parser.add_argument("--window_frames", type=int, default=0,
+                        help="0 (default): off. W > 0 (a multiple of 64; 512 = 4 s at 16 kHz is the benchmarked shape): a file whose spectrogram "
+                             "has more than W frames is enhanced in windows of at most W frames with cross-faded overlaps, so its memory does "
+                             "not grow with its length (--batch_size windows per sampler call). Departs from the reference, which has no such "
+                             "mode; shorter files are enhanced as without the switch")
+    parser.add_argument("--window_overlap", type=int, default=64,
+                        help="With --window_frames: frames by which neighbouring windows overlap and over which they are cross-faded "
+                             "(0 .. W/2 - 32)")
     parser.add_argument("--balance", type=str, choices=("contiguous", "frames"), default="contiguous",
                         help="Files per rank under torchrun: the reference's contiguous split of the sorted list (default), or balanced by "
                              "padded frame count (longest-processing-time); the enhanced files are identical either way")

@@ -343,51 +343,135 @@ class ScoreModel(nn.Module):
             return wave
         return wave, nfe, (time.time() - t_begin) / (len(wave) / self.sr)
 
+    def _batch_sampler(self, Y, N, corrector, corrector_steps, snr, noise, seed, predictor, sampler_type, use_graph, streams, corrector_scope,
+                       ode_kwargs):
+        """The zero-argument sampler of ``enhance_batch`` / ``enhance_long`` for spectrograms Y (a tensor [B,1,F,T] or a ragged list)."""
+        sb = type(self.sde).__name__ == "SBVESDE"
+        if ode_kwargs and (sb or sampler_type != "ode"):
+            raise TypeError(f"unexpected keyword arguments {sorted(ode_kwargs)} (get_ode_sampler's apply with sampler_type='ode' on an OUVE model)")
+        if sb:
+            return self.get_sb_sampler(sde=self.sde, y=Y, sampler_type="ode" if sampler_type == "pc" else sampler_type, noise=noise, seed=seed,
+                                       use_graph=use_graph, streams=streams)
+        if sampler_type == "pc":
+            return self.get_pc_sampler(predictor, corrector, Y, N=N, corrector_steps=corrector_steps, snr=snr, noise=noise, seed=seed,
+                                       use_graph=use_graph, streams=streams, corrector_scope=corrector_scope)
+        if sampler_type == "ode":
+            return self.get_ode_sampler(Y, N=N, noise=noise, seed=seed, use_graph=use_graph, streams=streams, **ode_kwargs)
+        raise ValueError(f"Sampler type {sampler_type} not supported")
+
     def enhance_batch(self, y, N=30, corrector="ald", corrector_steps=1, snr=0.5, pad_mode="zero_pad", noise=None, seed=None,
-                      predictor="reverse_diffusion", sampler_type="pc", use_graph=True, streams=None, corrector_scope="batch"):
+                      predictor="reverse_diffusion", sampler_type="pc", use_graph=True, streams=None, corrector_scope="batch", **ode_kwargs):
         """Batched form of enhancement.py:62-99: y float32 [B, L] (B utterances of equal length) -> enhanced float32 [B, L] on the
         model's device; or a LIST of 1-D waveforms of different lengths -> list of enhanced waveforms (one ragged batch, each
         utterance bit-identical to its own single call with the same seed and stream id; ``noise`` is then a list of
         [ndraws,1,F,T_b] tensors, T_b the padded frame count).  A Schroedinger-bridge model runs its own sampler, as in
         enhancement.build_sampler: 'ode' for ``sampler_type`` 'pc', else ``sampler_type``, with the model's own N.
-        ``corrector_scope='utterance'``: the 'langevin' corrector's step size per utterance (needed for a list).  Not in the
-        reference (which loops files one by one)."""
+        ``corrector_scope='utterance'``: the 'langevin' corrector's step size per utterance (needed for a list).  With
+        ``sampler_type='ode'`` further keyword arguments go to ``get_ode_sampler`` (``adaptive``, ``solver``, ``step_control``, ...).
+        Not in the reference (which loops files one by one)."""
         dev = self._device()
-        sb = type(self.sde).__name__ == "SBVESDE"
-        if sb:
-            sb_sampler = lambda Y, nz: self.get_sb_sampler(sde=self.sde, y=Y, sampler_type="ode" if sampler_type == "pc" else sampler_type,
-                                                           noise=nz, seed=seed, use_graph=use_graph, streams=streams)
+        make = lambda Y: self._batch_sampler(Y, N, corrector, corrector_steps, snr, noise, seed, predictor, sampler_type, use_graph, streams,
+                                             corrector_scope, ode_kwargs)
         if isinstance(y, (list, tuple)):
             # utterances of DIFFERENT lengths: one ragged batch (Context.set_frames) -- every utterance through its own STFT and
             # pad_spec, sampled together, inverted with its own length; returns a list of 1-D waveforms
             ys = [w.reshape(1, -1).to(dev) for w in y]
             norms = [w.abs().max() for w in ys]
             Ys = [pad_spec(self._forward_transform(self._stft(w / n)).unsqueeze(1), mode=pad_mode)[0] for w, n in zip(ys, norms)]
-            if sb:
-                sampler = sb_sampler(Ys, noise)
-            elif sampler_type == "pc":
-                sampler = self.get_pc_sampler(predictor, corrector, Ys, N=N, corrector_steps=corrector_steps, snr=snr, noise=noise, seed=seed,
-                                              use_graph=use_graph, streams=streams, corrector_scope=corrector_scope)
-            elif sampler_type == "ode":
-                sampler = self.get_ode_sampler(Ys, N=N, noise=noise, seed=seed, use_graph=use_graph, streams=streams)
-            else:
-                raise ValueError(f"Sampler type {sampler_type} not supported")
-            samples, nfe = sampler()
+            samples, nfe = make(Ys)()
             return [self.to_audio(s, w.size(1))[0] * n for s, w, n in zip(samples, ys, norms)], nfe
         y = y.to(dev)
         T_orig = y.size(1)
         norm = y.abs().amax(dim=1, keepdim=True)
         Y = self._forward_transform(self._stft(y / norm)).unsqueeze(1)
         Y = pad_spec(Y, mode=pad_mode)
-        if sb:
-            sampler = sb_sampler(Y, noise)
-        elif sampler_type == "pc":
-            sampler = self.get_pc_sampler(predictor, corrector, Y, N=N, corrector_steps=corrector_steps, snr=snr, noise=noise,
-                                          seed=seed, use_graph=use_graph, streams=streams, corrector_scope=corrector_scope)
-        elif sampler_type == "ode":
-            sampler = self.get_ode_sampler(Y, N=N, noise=noise, seed=seed, use_graph=use_graph, streams=streams)
-        else:
-            raise ValueError(f"Sampler type {sampler_type} not supported")
-        sample, nfe = sampler()
+        sample, nfe = make(Y)()
         x_hat = self.to_audio(sample[:, 0], T_orig) * norm
         return x_hat, nfe
+
+    # -- long recordings: windows with cross-faded overlaps (not in the reference) ------------------------------------------------
+    def _batch_coupling(self, sampler_type="pc", corrector="ald", corrector_scope="batch", adaptive=None, denoise=True, solver="scipy",
+                        step_control="batch", **_):
+        """Why this sampler configuration makes an utterance depend on what shares its batch (and what to use instead), or None."""
+        if type(self.sde).__name__ == "SBVESDE":
+            return None
+        if sampler_type == "pc" and corrector == "langevin" and corrector_scope != "utterance":
+            return ("the 'langevin' corrector at batch scope takes its step size from the batch-mean norms: pass corrector_scope='utterance' "
+                    "(every window's own norms)")
+        if sampler_type == "ode" and (adaptive if adaptive is not None else denoise is False):
+            if solver != "native":
+                return ("scipy's adaptive solver integrates the batch under one error norm: pass solver='native', step_control='utterance' "
+                        "(one step control per window)")
+            if step_control != "utterance":
+                return ("the adaptive solver with batch step control integrates the batch under one error norm: pass step_control='utterance' "
+                        "(one step control per window)")
+        return None
+
+    def enhance_long(self, y, window_frames=512, overlap_frames=64, batch_size=32, seed=None, stream=0, return_windows=False, **sampler_args):
+        """Enhancement of a recording of any length in windows of at most ``window_frames`` spectrogram frames whose neighbours
+        overlap by ``overlap_frames`` (up to 63 more for the last one) and are cross-faded: memory is bounded by ``batch_size``
+        windows instead of growing with the recording, and the network sees the context length it was trained on.  Not in the
+        reference, which enhances a recording as one spectrogram.  y: waveform [L] or [1, L]; ``sampler_args``: the sampler
+        arguments of ``enhance_batch`` (N, corrector, corrector_steps, snr, predictor, sampler_type, use_graph, corrector_scope, the
+        keywords of get_ode_sampler; pad_mode, used by a one-window recording only).
+
+        One peak over the whole recording and one STFT, as ``enhance``; the plan (util/windows.plan_windows; no window is padded);
+        spec_fwd + cut (sgmse_spec_split); the windows in order through sampler calls of up to ``batch_size`` windows -- a tensor when
+        all of a call's windows have ``window_frames`` frames, a ragged list when it holds the shorter last one --; spec_back +
+        cross-fade (sgmse_spec_merge: linear in the back-transformed domain, what a cross-fade of the two windows' waveforms would
+        be); one iSTFT to the input length; times the peak.  Window i draws its noise from stream ``stream + (i << 32)``: a window's
+        result depends on (seed, stream, i) and its own frames only, never on ``batch_size``.  A configuration that couples the
+        utterances of a batch would break that and raises ValueError for a recording of more than one window: 'langevin' at batch
+        scope, the adaptive ODE solver with solver='scipy' or with batch step control.
+
+        A recording of ONE window (K <= window_frames) takes the existing path, bit for bit: ``enhance_batch([y], streams=[stream])``
+        with pad_spec and ``pad_mode`` (a coupling configuration: the tensor form ``enhance_batch(y[None])``, which takes it).
+
+        Returns (waveform float32 [L] on the model's device, info): info['starts'], info['frames'] the plan, info['nfe'] the list of
+        the sampler calls' evaluation counts; with ``return_windows`` info['windows'], the enhanced windows [F,T_i] in the
+        transformed domain (None for a one-window recording, whose spectrogram the existing path does not return)."""
+        from .util.windows import plan_windows, window_stream
+        dev = self._device()
+        y = y.reshape(1, -1).to(dev)
+        L = y.size(1)
+        dm = self.data_module
+        K = L // dm.hop_length + 1 if dm.n_fft % 2 == 0 else (L - 1) // dm.hop_length + 1          # frames of the centred STFT (ops.stft)
+        starts, frames = plan_windows(K, window_frames, overlap_frames)
+        info = dict(starts=starts, frames=frames)
+        coupling = self._batch_coupling(**sampler_args)
+        if len(starts) == 1:
+            if coupling is None:
+                xs, nfe = self.enhance_batch([y[0]], seed=seed, streams=[stream], **sampler_args)
+            else:
+                xs, nfe = self.enhance_batch(y, seed=seed, streams=[stream], **sampler_args)
+            info["nfe"] = [nfe]
+            if return_windows:
+                info["windows"] = None
+            return xs[0], info
+        if coupling is not None:
+            raise ValueError(f"enhance_long: a recording of {len(starts)} windows would depend on batch_size: {coupling}")
+        if sampler_args.get("noise") is not None:
+            raise ValueError("enhance_long: replayed noise applies to a one-window recording only; windows draw from (seed, stream + (i << 32))")
+        args = dict(N=30, corrector="ald", corrector_steps=1, snr=0.5, noise=None, predictor="reverse_diffusion", sampler_type="pc",
+                    use_graph=True, corrector_scope="batch")
+        ode_kwargs = {k: v for k, v in sampler_args.items() if k not in args and k != "pad_mode"}
+        args.update({k: v for k, v in sampler_args.items() if k in args})
+        if seed is None:          # unseeded, like the reference's randn_like: one base seed for the recording's windows
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        batch_size = max(int(batch_size), 1)
+        peak = float(y.abs().max()) or 1.0
+        S = self._stft(y / peak)[0]                                      # [F,K], untransformed
+        wins = dm.split_windows(S, starts, frames)
+        ids = [window_stream(stream, i) for i in range(len(starts))]
+        outs, info["nfe"] = [], []
+        for lo in range(0, len(wins), batch_size):
+            hi = min(lo + batch_size, len(wins))
+            uniform = len(set(frames[lo:hi])) == 1
+            Y = torch.stack(wins[lo:hi]).unsqueeze(1) if uniform else wins[lo:hi]
+            sample, nfe = self._batch_sampler(Y, seed=seed, streams=ids[lo:hi], ode_kwargs=ode_kwargs, **args)()
+            outs += [s[0] for s in sample]                               # [1,F,T_i] -> [F,T_i]
+            info["nfe"].append(nfe)
+        x = self._istft(dm.merge_windows(outs, starts, frames, K), L) * peak
+        if return_windows:
+            info["windows"] = outs
+        return x, info

@@ -174,3 +174,34 @@ def spec_transform(spec: torch.Tensor, transform_type: str, factor: float, expon
     fn = ctx.lib.sgmse_spec_back if inverse else ctx.lib.sgmse_spec_fwd
     ctx.check(fn(ctx.h, s.data_ptr(), out.data_ptr(), s.numel(), _XF[transform_type], float(factor), float(exponent)))
     return out
+
+
+def spec_split(spec: torch.Tensor, starts, frames, transform_type: str, factor: float, exponent: float):
+    """The windows [:, starts[i] : starts[i] + frames[i]] of spec_fwd(spec), spec complex64 [F,K] untransformed: a list of [F,T_i]
+    views of ONE packed buffer (the layout a ragged batch takes), each bit-identical to that slice of ``spec_transform``'s output.
+    The plan (util/windows.plan_windows, or any other that covers [0, K) with at most two windows per frame) is checked by the library."""
+    if transform_type not in _XF:
+        raise NotImplementedError(f"transform_type {transform_type!r}")
+    ctx = default_context(spec.device)
+    packed = ctx.spec_split(spec, starts, frames, _XF[transform_type], factor, exponent)
+    return [w[0] for w in _lib._unpack_ragged(packed, [int(v) for v in frames], int(spec.shape[0]))]
+
+
+def spec_merge(windows, starts, frames, K: int, transform_type: str, factor: float, exponent: float) -> torch.Tensor:
+    """spec_back of the windows (a list of [F,T_i] or [1,F,T_i] tensors in the transformed domain, or their packed buffer) joined to
+    complex64 [F,K]: a frame under one window is ``spec_transform(..., inverse=True)`` of it, a frame under two is the linear
+    cross-fade of the two back-transformed values over the overlap (sgmse_spec_merge)."""
+    if transform_type not in _XF:
+        raise NotImplementedError(f"transform_type {transform_type!r}")
+    frames = [int(v) for v in frames]
+    if isinstance(windows, (list, tuple)):
+        ctx = default_context(windows[0].device)
+        got, F_ = _lib._ragged_geometry(windows, 1, "windows")
+        if got != frames:
+            raise ValueError(f"the windows have {got} frames, the plan says {frames}")
+        packed = torch.cat([_lib.check_tensor(w, "windows", torch.complex64, ctx.device).reshape(-1) for w in windows])
+    else:
+        ctx = default_context(windows.device)
+        packed = windows.reshape(-1)
+        F_ = packed.numel() // max(sum(frames), 1)
+    return ctx.spec_merge(packed, F_, int(K), starts, frames, _XF[transform_type], factor, exponent)
