@@ -83,6 +83,9 @@ const char* sgmse_last_error(sgmse_ctx* ctx);
 const char* sgmse_backend(void);                     /* "hip-gfx950" for the product library */
 
 /* -- model: replaces BackboneRegistry.get_by_name(name)(**kwargs) + load_state_dict (model.py:60-61,100-106) -- */
+/* Accepts nf in {32, 64, ..., 256}, 1-8 levels with nf * ch_mult[l] <= 256, num_res_blocks >= 1, up to 8 attention resolutions, both
+ * pyramids on or off, both variants.  Every attention block (the bottleneck's and those of attn_res) must stand at 32, 64, 128, 192 or
+ * 256 channels: anything else is SGMSE_EINVAL here, with the level's resolution and channel count in sgmse_last_error. */
 int sgmse_configure(sgmse_ctx* ctx, const sgmse_net_cfg* cfg);
 /* names = the reference state_dict keys of the backbone ("output_layer.weight", "all_modules.3.weight", ...;
  * ncsnpp.py:105,253), fp32, shapes as in the reference; every key of the configured network must be present.

@@ -97,14 +97,18 @@ int sgmse_configure(sgmse_ctx* ctx, const sgmse_net_cfg* cfg) {
   SG_ARG(ctx, cfg->progressive == 0 || cfg->progressive == 1, "progressive must be none or output_skip");
   SG_ARG(ctx, cfg->progressive_input == 0 || cfg->progressive_input == 1, "progressive_input must be none or input_skip");
   for (int i = 0; i < cfg->n_levels; ++i) SG_ARG(ctx, cfg->ch_mult[i] >= 1 && cfg->nf * cfg->ch_mult[i] <= 256, "ch_mult out of range");
-  return sg_guard(ctx, [&](sgmse::Engine& e) {
+  std::string bad;          // an attention block at a width the kernel has no instantiation for: refused here, not by the first forward
+  const int rc = sg_guard(ctx, [&](sgmse::Engine& e) {
     sgmse::NetCfg n;
     n.variant = cfg->variant; n.nf = cfg->nf; n.n_levels = cfg->n_levels; n.num_res_blocks = cfg->num_res_blocks;
     n.n_attn = cfg->n_attn; n.image_size = cfg->image_size; n.progressive = cfg->progressive;
     n.progressive_input = cfg->progressive_input; n.scale_by_sigma = cfg->scale_by_sigma;
     for (int i = 0; i < 8; ++i) { n.ch_mult[i] = cfg->ch_mult[i]; n.attn_res[i] = cfg->attn_res[i]; }
-    e.set_config(n);
+    bad = sgmse::attn_config_error(sgmse::build_layout(n));
+    if (bad.empty()) e.set_config(n);
   });
+  SG_ARG(ctx, rc != SGMSE_OK || bad.empty(), bad);
+  return rc;
 }
 
 int sgmse_load_weights(sgmse_ctx* ctx, const char* const* names, const void* const* ptrs, const long long* numels, int n,

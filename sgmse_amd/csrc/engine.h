@@ -47,6 +47,7 @@ struct Mod {
   enum Kind { FOURIER, LINEAR, CONV3, RES, ATTN, COMBINE, GN } kind;
   int idx, cin, cout;
   bool up, down;
+  int res;                    // resolution (rows) of the level the module runs at; 0 for the time-embedding modules
 };
 
 inline bool cfg_has_attn(const NetCfg& c, int res) {
@@ -56,18 +57,20 @@ inline bool cfg_has_attn(const NetCfg& c, int res) {
 
 inline std::vector<Mod> build_layout(const NetCfg& c) {
   std::vector<Mod> mods;
+  int res = 0;                // of the level being laid out
   auto add = [&](Mod::Kind k, int cin, int cout, bool up = false, bool down = false) {
-    mods.push_back(Mod{k, (int)mods.size(), cin, cout, up, down});
+    mods.push_back(Mod{k, (int)mods.size(), cin, cout, up, down, res});
   };
   const int nf = c.nf, L = c.n_levels, temb = 4 * nf, channels = 4;
   add(Mod::FOURIER, 0, nf);
   add(Mod::LINEAR, 2 * nf, temb);
   add(Mod::LINEAR, temb, temb);
+  res = c.image_size;
   add(Mod::CONV3, channels, nf);
   std::vector<int> hs_c{nf};
   int in_ch = nf;
   for (int l = 0; l < L; ++l) {
-    const int res = c.image_size >> l;
+    res = c.image_size >> l;
     for (int r = 0; r < c.num_res_blocks; ++r) {
       const int out_ch = nf * c.ch_mult[l];
       add(Mod::RES, in_ch, out_ch);
@@ -86,7 +89,7 @@ inline std::vector<Mod> build_layout(const NetCfg& c) {
   add(Mod::ATTN, in_ch, in_ch);
   add(Mod::RES, in_ch, in_ch);
   for (int l = L - 1; l >= 0; --l) {
-    const int res = c.image_size >> l;
+    res = c.image_size >> l;
     for (int r = 0; r < c.num_res_blocks + 1; ++r) {
       const int out_ch = nf * c.ch_mult[l];
       const int cin = in_ch + hs_c.back();
@@ -101,6 +104,16 @@ inline std::vector<Mod> build_layout(const NetCfg& c) {
   SG_REQUIRE(hs_c.empty(), "layout: skip stack not empty");
   if (c.progressive != 1) { add(Mod::GN, in_ch, in_ch); add(Mod::CONV3, in_ch, channels); }
   return mods;
+}
+
+// What launch_attn_core cannot run of a layout, as the text of the refusal, or "" (sgmse_configure refuses such a configuration as an
+// invalid argument, before weights are loaded: the first forward is too late to find out).
+inline std::string attn_config_error(const std::vector<Mod>& layout) {
+  for (const Mod& m : layout)
+    if (m.kind == Mod::ATTN && !attn_width_supported(m.cin))
+      return "attention block at resolution " + std::to_string(m.res) + " has " + std::to_string(m.cin) +
+             " channels; the attention kernel runs " + attn_widths_text() + " (choose ch_mult / attn_resolutions accordingly)";
+  return "";
 }
 
 // expected parameter names and element counts, in named_parameters() order
@@ -316,7 +329,12 @@ class Engine {
   void set_stream(void* s) { stream_ = reinterpret_cast<drt::stream_t>(s); }  // a captured graph can be launched on any stream
 
   // ---- weights ----------------------------------------------------------------------------------------------
-  void set_config(const NetCfg& c) { cfg_ = c; layout_ = build_layout(c); weights_ready_ = false; invalidate_graph(); read_knobs(); }
+  void set_config(const NetCfg& c) {
+    std::vector<Mod> layout = build_layout(c);
+    const std::string bad = attn_config_error(layout);
+    SG_REQUIRE(bad.empty(), bad);
+    cfg_ = c; layout_ = std::move(layout); weights_ready_ = false; invalidate_graph(); read_knobs();
+  }
   const NetCfg& config() const { return cfg_; }
 
   void load_weights(const char* const* names, const void* const* ptrs, const long long* numels, int n, int on_device) {
@@ -893,7 +911,7 @@ class Engine {
 
   void op_attention(const float* qkv, float* out, int B, int C, int S) {
     AttnArgs a{qkv, out, B, C, S, 1.0f / sqrtf((float)C), Rag{nullptr, nullptr, nullptr}, 0};
-    SG_REQUIRE(launch_attn_core(a, stream_), "attention: C must be 32, 64, 128 or 256");
+    SG_REQUIRE(launch_attn_core(a, stream_), "attention: C must be one of " + attn_widths_text());
     check_launch();
   }
 

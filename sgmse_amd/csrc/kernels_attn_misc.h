@@ -1,5 +1,6 @@
 // Self-attention core (MFMA), time-embedding MLP, network entry/exit and the sampler's element-wise updates.
 #pragma once
+#include <string>
 #include <sgmse_devrt.h>
 #include "kernels_conv.h"
 #include "kernels_norm_fir.h"
@@ -24,6 +25,7 @@ namespace sgmse {
 //      wave-private LDS tile with rows padded to 33 floats (bank = channel + key: conflict-free both ways) in chunks of 64
 //      channels; the A operand of P.V (lane = channel) is then one ds_read_b32.
 // LDS: q 32 KB + 4 x 8.4 KB (C = 256) = 66 KB and at most 256 registers: two workgroups per CU.
+// Instantiated for CF = C / 32 in SGMSE_ATTN_WIDTHS below (C = 192, the nf = 96 network: three V chunks, three K chunk pairs, 58 KB).
 struct AttnArgs { const float* qkv; float* out; int B, C, S; float scale; Rag rag; int H; };   // rag.w: S of utterance b = H * rag.w[b]
 
 template <int CF>
@@ -89,21 +91,28 @@ __global__ __launch_bounds__(256, 2) void attn_core_kernel(AttnArgs p) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) dst[i] = drt_buf_load(kbuf, lane_boff, (unsigned)(ch * 32 + 2 * i) * rowb);
     };
-    auto qk = [&](int ch, const float (&src)[16]) {
+    auto qk = [&](int ch, const float (&src)[16], f32x16& acc) {
 #pragma unroll
       for (int i = 0; i < 16; ++i)
-        sc = __builtin_amdgcn_mfma_f32_32x32x2f32(src[i], s_q[(ch * 32 + 2 * i + kh) * 32 + l31], sc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(src[i], s_q[(ch * 32 + 2 * i + kh) * 32 + l31], acc, 0, 0, 0);
     };
     load_k(0, ka0);
     if constexpr (CF == 1) {
-      qk(0, ka0);
+      qk(0, ka0, sc);
     } else {
+      // every chunk pair (64 channels) is summed in an accumulator of its own and then added to the score: a blocked sum, whose
+      // fp32 rounding error at 256 channels is about half that of one sequential 256-term chain
 #pragma unroll 1
       for (int ch = 0; ch < CF; ch += 2) {
+        f32x16 part;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) part[r] = 0.f;
         load_k(ch + 1, ka1);
-        qk(ch, ka0);
+        qk(ch, ka0, part);
         if (ch + 2 < CF) load_k(ch + 2, ka0);
-        qk(ch + 1, ka1);
+        qk(ch + 1, ka1, part);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sc[r] += part[r];
       }
     }
     float mx = NEG_INF;
@@ -182,13 +191,31 @@ __global__ __launch_bounds__(256, 2) void attn_core_kernel(AttnArgs p) {
   }
 }
 
+// The channel counts attn_core_kernel is instantiated for: the ONE list both the launcher below and the configuration check of the
+// engine (attn_config_error, engine.h) read.  The kernel's structure admits any even CF (V chunks of 64 channels, K chunk pairs) and CF = 1.
+#define SGMSE_ATTN_WIDTHS(X) X(1) X(2) X(4) X(6) X(8)
+
+constexpr bool attn_width_supported(int C) {
+#define SGMSE_ATTN_IS(CF) if (C == (CF) * 32) return true;
+  SGMSE_ATTN_WIDTHS(SGMSE_ATTN_IS)
+#undef SGMSE_ATTN_IS
+  return false;
+}
+
+inline std::string attn_widths_text() {          // "32, 64, 128, 192, 256" for the error messages
+  std::string s;
+#define SGMSE_ATTN_TXT(CF) s += (s.empty() ? "" : ", ") + std::to_string((CF) * 32);
+  SGMSE_ATTN_WIDTHS(SGMSE_ATTN_TXT)
+#undef SGMSE_ATTN_TXT
+  return s;
+}
+
 inline bool launch_attn_core(const AttnArgs& a, drt::stream_t st) {
   dim3 grid((a.S + 31) / 32, a.B, 1);
   switch (a.C) {
-    case 32: DRT_LAUNCH((attn_core_kernel<1>), grid, dim3(256), st, a); return true;
-    case 64: DRT_LAUNCH((attn_core_kernel<2>), grid, dim3(256), st, a); return true;
-    case 128: DRT_LAUNCH((attn_core_kernel<4>), grid, dim3(256), st, a); return true;
-    case 256: DRT_LAUNCH((attn_core_kernel<8>), grid, dim3(256), st, a); return true;
+#define SGMSE_ATTN_CASE(CF) case (CF) * 32: DRT_LAUNCH((attn_core_kernel<CF>), grid, dim3(256), st, a); return true;
+    SGMSE_ATTN_WIDTHS(SGMSE_ATTN_CASE)
+#undef SGMSE_ATTN_CASE
     default: return false;
   }
 }

@@ -1,0 +1,25 @@
+"""The attention kernel against float64 at every width, tile edge and logit range (attention_checks.py) on the hardware."""
+import pytest
+
+import attention_checks as A
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize("gain, mode", A.LOGITS)
+@pytest.mark.parametrize("S", A.LENGTHS)
+@pytest.mark.parametrize("C", A.WIDTHS)
+def test_attention_has_fp32_accuracy_against_fp64(hip, C, S, gain, mode):
+    A.check_attention_fp64(hip, C, S, gain, mode)
+
+
+@pytest.mark.parametrize("S", [1, 33, 97])
+@pytest.mark.parametrize("C", A.WIDTHS)
+def test_zero_queries_give_the_mean_of_v(hip, C, S):
+    A.check_attention_uniform(hip, C, S)
+
+
+@pytest.mark.parametrize("S", [33, 160])
+@pytest.mark.parametrize("C", A.WIDTHS)
+def test_an_utterance_alone_has_the_bits_it_has_in_a_batch(hip, C, S):
+    A.check_attention_batch_independence(hip, C, S)
