@@ -263,6 +263,16 @@ int sgmse_arena_bytes(sgmse_ctx* ctx, long long* out);
  * different batch size): utterance b uses stream b.  Replaces nothing in the reference (torch.randn_like draws depend on the
  * global generator state, sdes.py:229, correctors.py:74, predictors.py:62). */
 int sgmse_set_noise_streams(sgmse_ctx* ctx, const unsigned long long* ids, int n);
+/* Noise geometry (host arrays, one entry per utterance) for the NEXT sgmse_pc_sample / sgmse_sb_sample / sgmse_ode_sample /
+ * sgmse_ode_sample_each call of batch size n with in-kernel (Philox) noise, consumed like the stream ids: utterance b is the frames
+ * first_frame[b] .. first_frame[b] + T_b - 1 of a recording of total_frames[b] frames, and its element (f, t) draws at the counter
+ * index f * total_frames[b] + first_frame[b] + t instead of f * T_b + t (stream id and draw index unchanged).  Windows cut from one
+ * recording and given ONE stream id therefore draw one noise field: a frame under two windows sees the same draws in both.
+ * Default (no call, n = 0, or a different batch size): (0, T_b), today's index; an explicit (0, T_b) gives the same bits.  The
+ * geometry is device data like the seed: a captured step serves every geometry of its shape.  The sampler call returns
+ * SGMSE_EINVAL (the message names the utterance) if first_frame[b] < 0 or first_frame[b] + T_b > total_frames[b], and if it is
+ * given replayed noise (noise != NULL) together with a pending geometry.  Nothing in the reference corresponds. */
+int sgmse_set_noise_frames(sgmse_ctx* ctx, const int* first_frame, const int* total_frames, int n);
 /* Ragged batches: frames[b] = number of spectrogram frames T_b of utterance b (host array; each a multiple of 2^(levels-1), i.e.
  * of 64 -- what pad_spec produces) for ALL FOLLOWING sgmse_ncsnpp_forward / sgmse_pc_sample / sgmse_sb_sample / sgmse_ode_sample_each calls of batch size n, until the next
  * call (n = 0: uniform batches again).  Those calls then take T = max_b T_b and PACKED tensors: utterance after utterance, each

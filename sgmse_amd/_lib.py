@@ -91,6 +91,7 @@ _SIGS = {
     "sgmse_graph_captures": (_I, [_P, C.POINTER(_I)]),
     "sgmse_graph_updates": (_I, [_P, C.POINTER(_I)]),
     "sgmse_set_noise_streams": (_I, [_P, C.POINTER(C.c_ulonglong), _I]),
+    "sgmse_set_noise_frames": (_I, [_P, C.POINTER(_I), C.POINTER(_I), _I]),
     "sgmse_set_frames": (_I, [_P, C.POINTER(_I), _I]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -208,6 +209,7 @@ class Context:
         self.h = h
         self._keep: Dict[str, object] = {}
         self._frames: list = []          # frame table in force in the library (set_frames); [] = uniform batches
+        self._noise_frames_pending = False      # a noise geometry handed to the library that no sampler call has consumed yet
 
     def __del__(self):
         try:
@@ -255,6 +257,19 @@ class Context:
             if len(streams) != B:
                 raise ValueError(f"streams must name the {B} utterances of the batch, got {len(streams)}")
             self.set_noise_streams(streams)
+
+    def _take_noise_frames(self, noise_frames, B: int, noise) -> None:
+        """``noise_frames`` of a sampler call (None: the default geometry): checked against the batch and handed to the library, which
+        checks it against the utterances' frame counts in the call itself.  None withdraws a table an earlier, refused call left."""
+        if noise_frames is None:
+            if self._noise_frames_pending:
+                self.set_noise_frames([])
+            return
+        if len(noise_frames) != B:
+            raise ValueError(f"noise_frames must give (first_frame, total_frames) for the {B} utterances of the batch, got {len(noise_frames)}")
+        if noise is not None:
+            raise ValueError("noise_frames applies to in-kernel noise (seed / streams), not to replayed noise")
+        self.set_noise_frames(noise_frames)
 
     def _with_capturable_stream(self, run, use_graph) -> None:
         """``run()`` on the current stream, or, when it is to capture a graph there and cannot, on a side stream ordered with it."""
@@ -347,12 +362,12 @@ class Context:
     def pc_sample(self, Y: torch.Tensor, table: Dict[str, torch.Tensor], *, theta: float, std1: float,
                   corrector: str, corrector_steps: int, predictor: str, probability_flow: bool, denoise: bool,
                   noise: Optional[torch.Tensor], seed: int, use_graph: bool = True, affine=None, snr: float = 0.0, streams=None,
-                  corrector_scope: str = "batch"):
+                  corrector_scope: str = "batch", noise_frames=None):
         """``affine``: optional (in_scale, score_alpha, score_beta) fp32 tensors of length N: the score wrapper of
         ScoreModel.forward's new-code branch (ncsnpp_v2); None = old-code branch (score = -F).  ``corrector_scope``: 'batch' --
         the 'langevin' corrector takes its step size from the batch-mean norms (the reference) -- or 'utterance': from each
         utterance's own norms, what that utterance gets in a batch of its own (uniform and ragged batches).  ``noise`` of a ragged
-        batch: a list of [ndraws,1,F,T_b] tensors, one per utterance."""
+        batch: a list of [ndraws,1,F,T_b] tensors, one per utterance.  ``noise_frames``: see set_noise_frames."""
         if corrector_scope not in ("batch", "utterance"):
             raise ValueError(f"corrector_scope must be 'batch' or 'utterance', got {corrector_scope!r}")
         frames = None
@@ -397,6 +412,7 @@ class Context:
         out = torch.empty_like(Y)
         nfe = _I(0)
         self._take_streams(streams, B)
+        self._take_noise_frames(noise_frames, B, noise)
 
         def run():
             self.use_current_stream()
@@ -405,16 +421,17 @@ class Context:
             self.set_frames(frames if frames is not None else [])
             self.check(self.lib.sgmse_pc_sample(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, C.byref(cfg), ptr(noise),
                                                 C.c_ulonglong(seed & (2 ** 64 - 1)), C.byref(nfe)))
+            self._noise_frames_pending = False
 
         self._with_capturable_stream(run, use_graph)
         self._keep["sampler"] = (noise, keep)   # the captured graph refers to the replayed-noise buffer
         return (out if frames is None else _unpack_ragged(out, frames, F_)), nfe.value
 
     def sb_sample(self, Y: torch.Tensor, table: Dict[str, torch.Tensor], *, stochastic: bool, noise: Optional[torch.Tensor],
-                  seed: int, affine=None, use_graph: bool = True, streams=None):
+                  seed: int, affine=None, use_graph: bool = True, streams=None, noise_frames=None):
         """Schroedinger-bridge sampler; table: fp32 tensors t, w_prev, w_est, w_y, w_z of length N.  ``Y``: [B,1,F,T], or a ragged list
         of [F,T_b] / [1,F,T_b] spectrograms (``set_frames``; the samples come back as a list of [1,F,T_b], ``noise`` is then a list of
-        [ndraws,1,F,T_b] tensors)."""
+        [ndraws,1,F,T_b] tensors).  ``noise_frames``: see set_noise_frames."""
         frames = None
         if isinstance(Y, (list, tuple)):
             B = len(Y)
@@ -438,6 +455,7 @@ class Context:
         out = torch.empty_like(Y)
         nfe = _I(0)
         self._take_streams(streams, B)
+        self._take_noise_frames(noise_frames, B, noise)
 
         def run():
             self.use_current_stream()
@@ -445,6 +463,7 @@ class Context:
             self.check(self.lib.sgmse_sb_sample(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, N, *[fp(v) for v in keep],
                                                 *[None if v is None else fp(v) for v in aff], int(bool(stochastic)), ptr(noise),
                                                 C.c_ulonglong(seed & (2 ** 64 - 1)), int(bool(use_graph)), C.byref(nfe)))
+            self._noise_frames_pending = False
 
         self._with_capturable_stream(run, use_graph)
         self._keep["sb"] = (noise, keep, aff)
@@ -453,11 +472,12 @@ class Context:
     def ode_sample(self, Y: torch.Tensor, *, theta: float, sigma_min: float, sigma_max: float, std1: float, t_end: float, eps: float,
                    rtol: float, atol: float, first_step: float = 0.0, max_step: float = 0.0, noise: Optional[torch.Tensor] = None,
                    x0: Optional[torch.Tensor] = None, seed: int = 0, streams=None, affine_fn=None, max_nfe: int = 100000,
-                   step_control: str = "batch"):
+                   step_control: str = "batch", noise_frames=None):
         """Adaptive probability-flow sampler inside the library (sgmse_ode_sample): Dormand-Prince 5(4) with scipy's RK45 step
         control, state and stage slopes on the device.  ``x0``: the start state itself; else the prior y + std1 z with ``noise``
         ([B,1,F,T], or the samplers' [ndraws,B,1,F,T] layout whose first entry is the prior draw) or the Philox stream of
-        (``seed``, ``streams``).  ``affine_fn``: ``ScoreModel.score_affine`` of an ncsnpp_v2 model (None: old-code wrapper), called
+        (``seed``, ``streams``; ``noise_frames``: see set_noise_frames).  ``affine_fn``: ``ScoreModel.score_affine`` of an ncsnpp_v2
+        model (None: old-code wrapper), called
         with each attempted step's stage times.  Returns (sample, nfe); ``ode_stats`` describes the run.  Raises RuntimeError when
         the solver needs more than ``max_nfe`` evaluations or its step size underflows.
 
@@ -471,14 +491,15 @@ class Context:
         values = dict(theta=theta, sigma_min=sigma_min, sigma_max=sigma_max, std1=std1, t_end=t_end, eps=eps, rtol=rtol, atol=atol,
                       first_step=first_step, max_step=max_step, max_nfe=max_nfe)
         if step_control == "utterance":
-            return self._ode_sample_each(Y, values, noise, x0, seed, streams, affine_fn)
+            return self._ode_sample_each(Y, values, noise, x0, seed, streams, affine_fn, noise_frames)
         if isinstance(Y, (list, tuple)):
             raise TypeError("the adaptive ODE sampler integrates one rectangular batch (its error norm couples the utterances): "
                             "pass a tensor, not a ragged list")
         Y, noise, x0 = self._ode_rect_inputs(Y, noise, x0)
         # as in forward / pc_sample / sb_sample: a frame table left in force by an earlier ragged call is no request of this caller's
         # (a ragged batch is a list, refused above); a uniform call switches it off
-        return self._ode_call(self.lib.sgmse_ode_sample, Y, Y.shape[0], Y.shape[2], Y.shape[3], [], 1, values, noise, x0, seed, streams, affine_fn)
+        return self._ode_call(self.lib.sgmse_ode_sample, Y, Y.shape[0], Y.shape[2], Y.shape[3], [], 1, values, noise, x0, seed, streams, affine_fn,
+                              noise_frames)
 
     def _ode_rect_inputs(self, Y, noise, x0):
         """y [B,1,F,T] and the replayed noise or the start state of a rectangular batch, checked: (y, noise, x0)."""
@@ -500,12 +521,13 @@ class Context:
                 raise ValueError(f"the start state must have y's shape {tuple(Y.shape)}, got {tuple(x0.shape)}")
         return Y, noise, x0
 
-    def _ode_call(self, fn, Y, B, F_, T, frames, groups, values, noise, x0, seed, streams, affine_fn):
+    def _ode_call(self, fn, Y, B, F_, T, frames, groups, values, noise, x0, seed, streams, affine_fn, noise_frames=None):
         """One sgmse_ode_sample / sgmse_ode_sample_each call over checked inputs (``frames``: the ragged batch's frame table, [] for
         a rectangular one; ``groups``: controllers of the run, what ode_stats_each will list): (out, nfe).  An exception of the host
         callback is raised again here; a failed run raises RuntimeError."""
         cfg, failure, cb = self._ode_cfg(values, affine_fn)
         self._take_streams(streams, B)
+        self._take_noise_frames(noise_frames, B, noise)
         out = torch.empty_like(Y)
         nfe = _I(0)
         self.use_current_stream()
@@ -514,6 +536,7 @@ class Context:
         if failure:
             raise failure[0]
         self.check(rc)
+        self._noise_frames_pending = False
         self._ode_each_B = groups
         return out, nfe.value
 
@@ -541,12 +564,13 @@ class Context:
             cfg.coef_fn = cb
         return cfg, failure, cb
 
-    def _ode_sample_each(self, Y, values, noise, x0, seed, streams, affine_fn):
+    def _ode_sample_each(self, Y, values, noise, x0, seed, streams, affine_fn, noise_frames=None):
         """``ode_sample(step_control="utterance")``: sgmse_ode_sample_each over a tensor [B,1,F,T] or a ragged list."""
         if not isinstance(Y, (list, tuple)):
             Y, noise, x0 = self._ode_rect_inputs(Y, noise, x0)
             B, _, F_, T = Y.shape
-            return self._ode_call(self.lib.sgmse_ode_sample_each, Y, B, F_, T, [], B, values, noise, x0, seed, streams, affine_fn)
+            return self._ode_call(self.lib.sgmse_ode_sample_each, Y, B, F_, T, [], B, values, noise, x0, seed, streams, affine_fn,
+                                  noise_frames)
         if noise is not None:
             raise ValueError("ragged batches take the prior from seed / streams or a start state z, not from replayed noise")
         B = len(Y)
@@ -555,7 +579,8 @@ class Context:
             if not isinstance(x0, (list, tuple)) or len(x0) != B or _ragged_geometry(x0, 1, "z") != (frames, F_):
                 raise ValueError("the start state of a ragged batch is a list with the shapes of y's utterances")
             x0 = self._pack_ragged(x0, 1, "z")[0]
-        out, nfe = self._ode_call(self.lib.sgmse_ode_sample_each, Y, B, F_, max(frames), frames, B, values, None, x0, seed, streams, affine_fn)
+        out, nfe = self._ode_call(self.lib.sgmse_ode_sample_each, Y, B, F_, max(frames), frames, B, values, None, x0, seed, streams, affine_fn,
+                                  noise_frames)
         return _unpack_ragged(out, frames, F_), nfe
 
     def ode_stats_each(self):
@@ -629,6 +654,18 @@ class Context:
         ids = [int(v) & (2 ** 64 - 1) for v in (ids.tolist() if hasattr(ids, "tolist") else ids)]
         arr = (C.c_ulonglong * len(ids))(*ids)
         self.check(self.lib.sgmse_set_noise_streams(self.h, arr, len(ids)))
+
+    def set_noise_frames(self, noise_frames) -> None:
+        """Noise geometry, one (first_frame, total_frames) per utterance, for the next sampler call of that batch size with in-kernel
+        noise (sgmse_set_noise_frames): utterance b is the frames first_frame .. first_frame + T_b - 1 of a recording of total_frames
+        frames and draws the noise that recording's frames draw, so windows of one recording that share a stream id share the draws
+        of the frames they share.  [] withdraws a pending table.  The sampler call raises ValueError for a window that does not lie
+        inside its recording."""
+        pairs = [(int(a), int(b)) for a, b in noise_frames]
+        n = len(pairs)
+        first, total = (_I * max(n, 1))(*[p[0] for p in pairs]), (_I * max(n, 1))(*[p[1] for p in pairs])
+        self.check(self.lib.sgmse_set_noise_frames(self.h, first if n else None, total if n else None, n))
+        self._noise_frames_pending = n > 0
 
     def set_frames(self, frames) -> None:
         """Ragged batches (sgmse_set_frames): frame count of every utterance of the following calls; [] = uniform batches again."""

@@ -16,6 +16,9 @@ int sg_guard(sgmse_ctx* ctx, Fn&& fn) {
   try {
     fn(*ctx->eng);
     return SGMSE_OK;
+  } catch (const sgmse::EngineArgError& e) {
+    ctx->err = std::string("invalid argument: ") + e.what();
+    return SGMSE_EINVAL;
   } catch (const sgmse::EngineError& e) {
     ctx->err = e.what();
     const bool notready = ctx->err.find("weights not loaded") != std::string::npos;
@@ -287,6 +290,11 @@ int sgmse_arena_bytes(sgmse_ctx* ctx, long long* out) {
 int sgmse_set_noise_streams(sgmse_ctx* ctx, const unsigned long long* ids, int n) {
   SG_ARG(ctx, (ids != nullptr && n > 0) || n == 0, "bad stream table");
   return sg_guard(ctx, [&](sgmse::Engine& e) { e.set_noise_streams(ids, n); });
+}
+
+int sgmse_set_noise_frames(sgmse_ctx* ctx, const int* first_frame, const int* total_frames, int n) {
+  SG_ARG(ctx, (first_frame != nullptr && total_frames != nullptr && n > 0) || n == 0, "bad noise-frame table");
+  return sg_guard(ctx, [&](sgmse::Engine& e) { e.set_noise_frames(first_frame, total_frames, n); });
 }
 
 int sgmse_set_frames(sgmse_ctx* ctx, const int* frames, int n) {

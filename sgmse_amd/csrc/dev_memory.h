@@ -11,6 +11,8 @@
 namespace sgmse {
 
 struct EngineError : std::runtime_error { using std::runtime_error::runtime_error; };
+// an argument the engine can only judge inside a call (the C boundary reports SGMSE_EINVAL, not SGMSE_ERUNTIME)
+struct EngineArgError : EngineError { using EngineError::EngineError; };
 
 #define SG_CHECK(expr) do { int _e = (expr); if (_e != 0) { char _b[256]; snprintf(_b, sizeof _b, "%s failed: %s (%d)", #expr, drt::error_string(_e), _e); throw EngineError(_b); } } while (0)
 #define SG_REQUIRE(cond, msg) do { if (!(cond)) throw EngineError(std::string(msg)); } while (0)

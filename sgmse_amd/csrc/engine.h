@@ -457,6 +457,7 @@ class Engine {
     SG_REQUIRE(sc.N >= 1 && sc.t && sc.dt && sc.G && sc.G2, "pc_sample: step table missing");
     SG_REQUIRE(sc.corrector != 1 || (sc.ald_eps && sc.ald_noise), "pc_sample: ALD table missing");
     ensure_shape(B, F, T, sc.N);
+    take_noise_frames("pc_sample", B, T, noise);
     SG_REQUIRE(!ragged() || sc.corrector != 2, "ragged batches: the Langevin corrector with the step size of the batch couples the utterances (correctors.py:50-52) "
                                                "and is not supported; corrector = 3 takes the step size per utterance");
     const size_t n = ragged() ? rag_[0].pix : (size_t)B * F * T;     // complex elements of Y / the result, utterance after utterance
@@ -525,6 +526,7 @@ class Engine {
     require_ready();
     SG_REQUIRE(N >= 1 && t && w_prev && w_est && w_y && w_z, "sb_sample: step table missing");
     ensure_shape(B, F, T, N);
+    take_noise_frames("sb_sample", B, T, noise);
     const size_t n = ragged() ? rag_[0].pix : (size_t)B * F * T;     // complex elements of Y / the result, utterance after utterance
     const StepSetup st = begin_steps("sb_sample", Y, n, B, N, seed, [&](int i, float* r) {
       r[SC_T] = t[i]; r[SB_WPREV] = w_prev[i]; r[SB_WEST] = w_est[i]; r[SB_WY] = w_y[i]; r[SB_WZ] = w_z[i];
@@ -584,6 +586,7 @@ class Engine {
     SG_REQUIRE(!per_utterance || B <= kOdeEachMaxB, "ode_sample_each: batch too large");
     const int G = per_utterance ? B : 1;
     ensure_shape(B, F, T, ODE_ROWS * G);
+    take_noise_frames(who, B, T, noise);
     const size_t n = ragged() ? rag_[0].pix : (size_t)B * F * T;     // complex elements, utterance after utterance
     const size_t per = per_utterance ? (size_t)F * T : n;            // ... of a group (ragged: of the longest)
     for (DevArray<float2>& k : ode_k_) grow(k, n * 8);
@@ -758,6 +761,30 @@ class Engine {
     else { if (accepted) *accepted = 0; if (rejected) *rejected = 0; }
   }
   void set_noise_streams(const unsigned long long* ids, int n) { streams_next_.assign(ids, ids + n); }
+  void set_noise_frames(const int* first, const int* total, int n) {
+    frames_next_.assign(first, first + n);
+    frames_next_.insert(frames_next_.end(), total, total + n);
+  }
+  // The noise geometry of the sampler call `who` over B utterances of T frames (ragged: the frame table's) -> geom_call_, which
+  // upload_tables puts behind the stream ids.  A pending table of B entries is consumed and checked -- a refusal also drops the
+  // pending stream ids, which belonged to the same call --, one of another size is dropped like stream ids of another size.
+  void take_noise_frames(const std::string& who, int B, int T, const float2* noise) {
+    std::vector<int> g;
+    g.swap(frames_next_);
+    geom_call_.clear();
+    if ((int)g.size() != 2 * B) return;
+    std::string bad;
+    if (noise) bad = who + ": a noise geometry (sgmse_set_noise_frames) applies to in-kernel noise, not to replayed noise";
+    for (int b = 0; b < B && bad.empty(); ++b) {
+      const int Tb = ragged() ? rag_T_[b] : T;
+      const long long first = g[b], total = g[B + b];
+      if (first < 0 || first + Tb > total)
+        bad = who + ": utterance " + std::to_string(b) + ": noise frames [" + std::to_string(first) + ", " + std::to_string(first + Tb) +
+              ") do not lie inside the recording's [0, " + std::to_string(total) + ")";
+      geom_call_.insert(geom_call_.end(), {g[b], g[B + b], Tb});
+    }
+    if (!bad.empty()) { geom_call_.clear(); streams_next_.clear(); throw EngineArgError(bad); }
+  }
   void set_ragged_frames(const int* frames, int n) { set_frames(frames, n); }     // sgmse_set_frames
   int last_nfe() const { return nfe_; }
   int graph_captures() const { return graph_captures_; }     // how many times a step was captured + instantiated (tests, bench)
@@ -2028,18 +2055,23 @@ class Engine {
   } stage_;
   // Per-call sampler constants -> device (through stage_): the step table, the time steps, the score-wrapper rows (may be empty) and
   // the noise table -- seed word + one noise-stream id per utterance (SamplerArgs::seed; ids given by set_noise_streams are consumed
-  // by the next sampler call of the same batch size, otherwise utterance b gets stream b).
+  // by the next sampler call of the same batch size, otherwise utterance b gets stream b), then the noise geometry of the call
+  // (take_noise_frames) in the layout SamplerArgs::seed describes.
   const unsigned long long* upload_tables(const std::vector<float>& tab, const std::vector<float>& tv, const std::vector<float>& cf,
                                           unsigned long long seed, int B) {
     SG_REQUIRE(B + 1 <= kMaxStreams, "batch too large for the noise-stream table");
-    grow(seed_dev_, (size_t)kMaxStreams * 8);
-    const size_t nb_seed = ((size_t)B + 1) * 8, nb_tab = tab.size() * 4, nb_tv = tv.size() * 4, nb_cf = cf.size() * 4;
+    grow(seed_dev_, (size_t)kMaxStreams * (8 + 12) + 8);      // seed + ids, the geometry flag, three ints per utterance
+    const size_t nb_geom = geom_call_.empty() ? 0 : ((size_t)3 * B * 4 + 7) / 8 * 8;
+    const size_t nb_seed = ((size_t)B + 2) * 8 + nb_geom, nb_tab = tab.size() * 4, nb_tv = tv.size() * 4, nb_cf = cf.size() * 4;
     char* q = stage_.acquire(nb_seed + nb_tab + nb_tv + nb_cf);
     unsigned long long* hs = reinterpret_cast<unsigned long long*>(q);
     hs[0] = seed;
     const bool given = (int)streams_next_.size() == B;
     for (int b = 0; b < B; ++b) hs[1 + b] = given ? streams_next_[b] : (unsigned long long)b;
     streams_next_.clear();
+    hs[1 + B] = nb_geom ? 1ull : 0ull;                        // the noise geometry of this call (take_noise_frames), if any
+    if (nb_geom) { hs[1 + B + nb_geom / 8] = 0; memcpy(hs + 2 + B, geom_call_.data(), (size_t)3 * B * 4); }
+    geom_call_.clear();
     q += nb_seed;
     memcpy(q, tab.data(), nb_tab); memcpy(q + nb_tab, tv.data(), nb_tv);
     if (nb_cf) memcpy(q + nb_tab + nb_tv, cf.data(), nb_cf);
@@ -2052,6 +2084,8 @@ class Engine {
   }
   static constexpr int kMaxStreams = 4096;
   std::vector<unsigned long long> streams_next_;
+  std::vector<int> frames_next_;      // pending noise geometry (set_noise_frames): [first_frame x n][total_frames x n]
+  std::vector<int> geom_call_;        // ... of the running sampler call, checked: (first_frame, total_frames, T_b) per utterance; empty: default
   DevArray<unsigned long long> seed_dev_;
   DevArray<int> win_tab_;             // window plan of the last spec_split / spec_merge
   int graph_captures_ = 0;

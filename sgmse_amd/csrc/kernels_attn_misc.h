@@ -402,6 +402,10 @@ struct SamplerArgs {
   // the noise-stream id of utterance b.  An utterance's draws depend on (seed, stream id, element index INSIDE the utterance,
   // draw): with stream ids that name the utterance (the directory script: index in the file list) its noise, and with it the
   // enhanced file, does not depend on how the corpus was batched or sharded.  Default stream id: the batch slot.
+  // Behind the B stream ids, the noise geometry (sgmse_set_noise_frames), device data like the seed so that a captured step serves
+  // every geometry of its shape: seed[1 + B] != 0 iff one was given, then three ints per utterance, (first_frame, total_frames, T_b).
+  // Element (f, t) of utterance b draws at counter index f * total_frames + first_frame + t: the index of frame first_frame + t of a
+  // recording of total_frames frames, so that windows cut from one recording, given its stream id, draw one noise field.
   const unsigned long long* seed;
   const float* table; const int* step_ptr;
   int draw_base, draw_per_step;  // draw index = draw_base + step*draw_per_step
@@ -429,10 +433,19 @@ __device__ __forceinline__ int sampler_utt(const SamplerArgs& p, int i, long lon
   return b;
 }
 
+// Philox counter index of the element k = f * T_b + t of utterance b: k itself without a noise geometry (one uniform load and a
+// branch the whole wave takes the same way; no division), else f * total_frames + first_frame + t -- which is k again for (0, T_b)
+__device__ __forceinline__ unsigned long long sampler_noise_index(const SamplerArgs& p, unsigned k, int b) {
+  if (p.seed[1 + p.B] == 0) return k;
+  const int* g = reinterpret_cast<const int*>(p.seed + 2 + p.B) + 3 * b;
+  const unsigned Tb = (unsigned)g[2], f = k / Tb;
+  return (unsigned long long)f * (unsigned long long)g[1] + (unsigned long long)g[0] + (unsigned long long)(k - f * Tb);
+}
+
 // the draw of element i, which lies in utterance b starting at `first`
 __device__ __forceinline__ float2 sampler_noise_of(const SamplerArgs& p, int i, int draw, int b, long long first) {
   if (p.noise) return p.noise[(size_t)draw * p.n + i];
-  return philox_cnormal(p.seed[0], (unsigned long long)((long long)i - first), (uint32_t)draw, p.seed[1 + b]);
+  return philox_cnormal(p.seed[0], sampler_noise_index(p, (unsigned)((long long)i - first), b), (uint32_t)draw, p.seed[1 + b]);
 }
 
 __device__ __forceinline__ float2 sampler_noise(const SamplerArgs& p, int i, int draw) {

@@ -24,7 +24,8 @@ Differences from the reference script, none of them in the arithmetic of one utt
   windows of at most W frames that overlap by ``--window_overlap`` frames and are cross-faded (``ScoreModel.enhance_long``): its
   memory no longer grows with its length and the network sees the context length it was trained on.  THIS DEPARTS FROM THE
   REFERENCE, which has no such mode and enhances every recording as one spectrogram: a windowed file is not what the reference
-  computes for it.  Files of at most W frames stay in the batches above, unchanged;
+  computes for it.  Files of at most W frames stay in the batches above, unchanged.  ``--window_noise recording`` gives the
+  windows of a file one noise field, indexed by the file's frame, instead of one unrelated field per window;
 * audio I/O uses ``soundfile`` when it is installed; otherwise ``scipy.io.wavfile`` for wav and the package's own decoder
   (util/flac.py) for flac input; resampling to the
   model's rate uses ``scipy.signal.resample_poly`` (the reference: ``librosa.resample``).
@@ -301,7 +302,7 @@ def enhance_long_files(model: ScoreModel, files: List[str], test_dir: str, enhan
     for path, g in zip(files, gidx):
         y = torch.from_numpy(_load_wave(path, target_sr))
         x, _ = model.enhance_long(y, window_frames=args.window_frames, overlap_frames=args.window_overlap, batch_size=args.batch_size,
-                                  seed=args.seed, stream=g, **kw)
+                                  seed=args.seed, stream=g, window_noise=getattr(args, "window_noise", None) or "window", **kw)
         name = path.replace(test_dir, "")
         name = name[1:] if name.startswith("/") else name
         write_audio(join(enhanced_dir, name), x.cpu().numpy(), target_sr)
@@ -489,11 +490,17 @@ def main(argv=None) -> int:
     parser.add_argument("--window_overlap", type=int, default=64,
                         help="With --window_frames: frames by which neighbouring windows overlap and over which they are cross-faded "
                              "(0 .. W/2 - 32)")
+    parser.add_argument("--window_noise", type=str, choices=("window", "recording"), default=None,
+                        help="With --window_frames: 'window' (the default) = every window draws its own noise, so the frames two windows "
+                             "share are cross-faded between two independent samples; 'recording' = one noise field per file, indexed by the "
+                             "file's frame, which the windows over a frame share")
     parser.add_argument("--balance", type=str, choices=("contiguous", "frames"), default="contiguous",
                         help="Files per rank under torchrun: the reference's contiguous split of the sorted list (default), or balanced by "
                              "padded frame count (longest-processing-time); the enhanced files are identical either way")
     parser.add_argument("--io_threads", type=int, default=4, help="Background threads that read / resample the next batches' files")
     args = parser.parse_args(argv)
+    if args.window_noise is not None and args.window_frames <= 0:
+        raise ValueError("--window_noise applies to windowed enhancement: pass --window_frames")
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     device = torch.device(args.device)

@@ -232,7 +232,7 @@ class ScoreModel(nn.Module):
     # -- samplers (reference model.py:348-390) -----------------------------------------------------------------
     @staticmethod
     def _minibatch_kwargs(kwargs, lo, hi):
-        """Sampler keyword arguments of the serial chunk [lo, hi) of a batch: replayed noise and noise-stream ids are per
+        """Sampler keyword arguments of the serial chunk [lo, hi) of a batch: replayed noise, noise-stream ids and noise geometry are per
         utterance; without explicit stream ids a chunk's utterances keep the ids they have in the whole batch (their position),
         so that chunked and unchunked runs of one seed draw the same noise."""
         kw = dict(kwargs)
@@ -241,6 +241,8 @@ class ScoreModel(nn.Module):
         elif kw.get("noise") is not None:
             kw["noise"] = kw["noise"][:, lo:hi].contiguous()
         kw["streams"] = list(range(lo, hi)) if kw.get("streams") is None else list(kw["streams"][lo:hi])
+        if kw.get("noise_frames") is not None:                # the noise geometry is per utterance too
+            kw["noise_frames"] = list(kw["noise_frames"][lo:hi])
         return kw
 
     def _chunked(self, make_sampler, y, minibatch, kwargs):
@@ -344,34 +346,38 @@ class ScoreModel(nn.Module):
         return wave, nfe, (time.time() - t_begin) / (len(wave) / self.sr)
 
     def _batch_sampler(self, Y, N, corrector, corrector_steps, snr, noise, seed, predictor, sampler_type, use_graph, streams, corrector_scope,
-                       ode_kwargs):
+                       ode_kwargs, noise_frames=None, minibatch=None):
         """The zero-argument sampler of ``enhance_batch`` / ``enhance_long`` for spectrograms Y (a tensor [B,1,F,T] or a ragged list)."""
         sb = type(self.sde).__name__ == "SBVESDE"
         if ode_kwargs and (sb or sampler_type != "ode"):
             raise TypeError(f"unexpected keyword arguments {sorted(ode_kwargs)} (get_ode_sampler's apply with sampler_type='ode' on an OUVE model)")
+        extra = {k: v for k, v in (("noise_frames", noise_frames), ("minibatch", minibatch)) if v is not None}
         if sb:
             return self.get_sb_sampler(sde=self.sde, y=Y, sampler_type="ode" if sampler_type == "pc" else sampler_type, noise=noise, seed=seed,
-                                       use_graph=use_graph, streams=streams)
+                                       use_graph=use_graph, streams=streams, **extra)
         if sampler_type == "pc":
             return self.get_pc_sampler(predictor, corrector, Y, N=N, corrector_steps=corrector_steps, snr=snr, noise=noise, seed=seed,
-                                       use_graph=use_graph, streams=streams, corrector_scope=corrector_scope)
+                                       use_graph=use_graph, streams=streams, corrector_scope=corrector_scope, **extra)
         if sampler_type == "ode":
-            return self.get_ode_sampler(Y, N=N, noise=noise, seed=seed, use_graph=use_graph, streams=streams, **ode_kwargs)
+            return self.get_ode_sampler(Y, N=N, noise=noise, seed=seed, use_graph=use_graph, streams=streams, **extra, **ode_kwargs)
         raise ValueError(f"Sampler type {sampler_type} not supported")
 
     def enhance_batch(self, y, N=30, corrector="ald", corrector_steps=1, snr=0.5, pad_mode="zero_pad", noise=None, seed=None,
-                      predictor="reverse_diffusion", sampler_type="pc", use_graph=True, streams=None, corrector_scope="batch", **ode_kwargs):
+                      predictor="reverse_diffusion", sampler_type="pc", use_graph=True, streams=None, corrector_scope="batch", noise_frames=None,
+                      minibatch=None, **ode_kwargs):
         """Batched form of enhancement.py:62-99: y float32 [B, L] (B utterances of equal length) -> enhanced float32 [B, L] on the
         model's device; or a LIST of 1-D waveforms of different lengths -> list of enhanced waveforms (one ragged batch, each
         utterance bit-identical to its own single call with the same seed and stream id; ``noise`` is then a list of
         [ndraws,1,F,T_b] tensors, T_b the padded frame count).  A Schroedinger-bridge model runs its own sampler, as in
         enhancement.build_sampler: 'ode' for ``sampler_type`` 'pc', else ``sampler_type``, with the model's own N.
-        ``corrector_scope='utterance'``: the 'langevin' corrector's step size per utterance (needed for a list).  With
+        ``corrector_scope='utterance'``: the 'langevin' corrector's step size per utterance (needed for a list).  ``noise_frames``: one
+        (first_frame, total_frames) per utterance, in PADDED spectrogram frames (sampling.get_pc_sampler); ``minibatch``: the batch in
+        serial chunks of that many utterances, each with its own slice of ``noise`` / ``streams`` / ``noise_frames``.  With
         ``sampler_type='ode'`` further keyword arguments go to ``get_ode_sampler`` (``adaptive``, ``solver``, ``step_control``, ...).
         Not in the reference (which loops files one by one)."""
         dev = self._device()
         make = lambda Y: self._batch_sampler(Y, N, corrector, corrector_steps, snr, noise, seed, predictor, sampler_type, use_graph, streams,
-                                             corrector_scope, ode_kwargs)
+                                             corrector_scope, ode_kwargs, noise_frames, minibatch)
         if isinstance(y, (list, tuple)):
             # utterances of DIFFERENT lengths: one ragged batch (Context.set_frames) -- every utterance through its own STFT and
             # pad_spec, sampled together, inverted with its own length; returns a list of 1-D waveforms
@@ -407,7 +413,8 @@ class ScoreModel(nn.Module):
                         "(one step control per window)")
         return None
 
-    def enhance_long(self, y, window_frames=512, overlap_frames=64, batch_size=32, seed=None, stream=0, return_windows=False, **sampler_args):
+    def enhance_long(self, y, window_frames=512, overlap_frames=64, batch_size=32, seed=None, stream=0, return_windows=False,
+                     window_noise="window", **sampler_args):
         """Enhancement of a recording of any length in windows of at most ``window_frames`` spectrogram frames whose neighbours
         overlap by ``overlap_frames`` (up to 63 more for the last one) and are cross-faded: memory is bounded by ``batch_size``
         windows instead of growing with the recording, and the network sees the context length it was trained on.  Not in the
@@ -424,13 +431,22 @@ class ScoreModel(nn.Module):
         utterances of a batch would break that and raises ValueError for a recording of more than one window: 'langevin' at batch
         scope, the adaptive ODE solver with solver='scipy' or with batch step control.
 
+        ``window_noise``: 'window' (default) -- the above: every window its own stream, indexed inside the window, so a frame under
+        two windows gets two unrelated noise realisations and the cross-fade averages two independent samples; 'recording' -- ONE
+        noise field for the recording: every window draws from the recording's own id ``stream`` at the counter of the recording's
+        frame (noise geometry (starts[i], K), sgmse_set_noise_frames), so both windows over a frame see the same draws there and
+        differ only by what the network makes of their different context.  Still a function of (seed, stream, i) and the window's
+        frames, never of ``batch_size``.  Any other value raises ValueError.
+
         A recording of ONE window (K <= window_frames) takes the existing path, bit for bit: ``enhance_batch([y], streams=[stream])``
         with pad_spec and ``pad_mode`` (a coupling configuration: the tensor form ``enhance_batch(y[None])``, which takes it).
 
         Returns (waveform float32 [L] on the model's device, info): info['starts'], info['frames'] the plan, info['nfe'] the list of
         the sampler calls' evaluation counts; with ``return_windows`` info['windows'], the enhanced windows [F,T_i] in the
         transformed domain (None for a one-window recording, whose spectrogram the existing path does not return)."""
-        from .util.windows import plan_windows, window_stream
+        from .util.windows import WINDOW_NOISE, plan_windows, window_noise_plan
+        if window_noise not in WINDOW_NOISE:
+            raise ValueError(f"window_noise must be 'window' or 'recording', got {window_noise!r}")
         dev = self._device()
         y = y.reshape(1, -1).to(dev)
         L = y.size(1)
@@ -451,7 +467,8 @@ class ScoreModel(nn.Module):
         if coupling is not None:
             raise ValueError(f"enhance_long: a recording of {len(starts)} windows would depend on batch_size: {coupling}")
         if sampler_args.get("noise") is not None:
-            raise ValueError("enhance_long: replayed noise applies to a one-window recording only; windows draw from (seed, stream + (i << 32))")
+            raise ValueError("enhance_long: replayed noise applies to a one-window recording only; windows draw from (seed, stream + (i << 32)) "
+                             "or, with window_noise='recording', from (seed, stream) at the recording's frames")
         args = dict(N=30, corrector="ald", corrector_steps=1, snr=0.5, noise=None, predictor="reverse_diffusion", sampler_type="pc",
                     use_graph=True, corrector_scope="batch")
         ode_kwargs = {k: v for k, v in sampler_args.items() if k not in args and k != "pad_mode"}
@@ -460,15 +477,19 @@ class ScoreModel(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         batch_size = max(int(batch_size), 1)
         peak = float(y.abs().max()) or 1.0
-        S = self._stft(y / peak)[0]                                      # [F,K], untransformed
+        ids, geom = window_noise_plan(stream, starts, K, window_noise)
+        # 'recording' divides by the peak as enhance_batch does, by a tensor on the device: on a GPU torch turns a division by a
+        # Python number into a multiplication by its reciprocal, an ulp apart in one sample of six (measured on MI355X), which alone
+        # would keep a windowed run from being the one-spectrogram run where nothing else does.  'window' keeps the form it has.
+        S = self._stft(y / (peak if geom is None else y.new_tensor(peak)))[0]       # [F,K], untransformed
         wins = dm.split_windows(S, starts, frames)
-        ids = [window_stream(stream, i) for i in range(len(starts))]
         outs, info["nfe"] = [], []
         for lo in range(0, len(wins), batch_size):
             hi = min(lo + batch_size, len(wins))
             uniform = len(set(frames[lo:hi])) == 1
             Y = torch.stack(wins[lo:hi]).unsqueeze(1) if uniform else wins[lo:hi]
-            sample, nfe = self._batch_sampler(Y, seed=seed, streams=ids[lo:hi], ode_kwargs=ode_kwargs, **args)()
+            sample, nfe = self._batch_sampler(Y, seed=seed, streams=ids[lo:hi], ode_kwargs=ode_kwargs,
+                                              noise_frames=None if geom is None else geom[lo:hi], **args)()
             outs += [s[0] for s in sample]                               # [1,F,T_i] -> [F,T_i]
             info["nfe"].append(nfe)
         x = self._istft(dm.merge_windows(outs, starts, frames, K), L) * peak

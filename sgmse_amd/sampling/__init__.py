@@ -43,10 +43,17 @@ def _require_native_for_ragged(ctx, y):
                         "get_sb_sampler; no force_python_loop")
 
 
+def _require_native_for_noise_frames(ctx, noise_frames):
+    """A noise geometry (Context.set_noise_frames) indexes the in-kernel Philox noise: only the library loops draw it."""
+    if ctx is None and noise_frames is not None:
+        raise ValueError("noise_frames applies to the in-kernel noise of the native HIP samplers (seed / streams); this configuration runs "
+                         "the Python loop, which draws from torch's generator")
+
+
 def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=True, eps=3e-2, snr=0.1, corrector_steps=1,
                    probability_flow: bool = False, intermediate=False, noise: Optional[torch.Tensor] = None,
                    seed: Optional[int] = None, use_graph: bool = True, force_python_loop: bool = False, streams=None,
-                   corrector_scope: str = "batch", **kwargs):
+                   corrector_scope: str = "batch", noise_frames=None, **kwargs):
     """Predictor-corrector sampler (reference sampling/__init__.py:26-70).
 
     Extra keyword arguments of this implementation: ``noise`` (complex64 [ndraws,B,1,F,T] replayed standard-normal
@@ -56,7 +63,9 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=Tru
     ``force_python_loop``, ``corrector_scope`` ('batch': the 'langevin' corrector takes its step size from the batch-mean norms, as
     the reference does; 'utterance': from each utterance's own norms, so an utterance gets what the reference's one-file-at-a-time
     loop gives it and ``y`` may be a ragged list; accepted with every corrector, it only matters for 'langevin').  With a ragged
-    list ``y``, ``noise`` is a list of [ndraws,1,F,T_b] tensors."""
+    list ``y``, ``noise`` is a list of [ndraws,1,F,T_b] tensors.  ``noise_frames``: one (first_frame, total_frames) per utterance --
+    the utterance is that stretch of a recording of total_frames frames and draws the noise those frames draw (Context.set_noise_frames),
+    so windows of one recording that share a stream id carry ONE noise field; default: an utterance is its own recording."""
     if corrector_scope not in ("batch", "utterance"):
         raise ValueError(f"corrector_scope must be 'batch' or 'utterance', got {corrector_scope!r}")
     predictor_cls = PredictorRegistry.get_by_name(predictor_name)   # ValueError for unknown names, like the reference
@@ -66,6 +75,7 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=Tru
               and isinstance(sde, OUVESDE) and not intermediate)
     ctx = _native_engine(score_fn, y) if native else None
     _require_native_for_ragged(ctx, y)
+    _require_native_for_noise_frames(ctx, noise_frames)
 
     if ctx is not None:
         table = sde.step_table(eps, snr, sde.N)
@@ -78,7 +88,8 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=Tru
                 out, nfe = ctx.pc_sample(y, table, theta=float(sde.theta), std1=std1, corrector=corrector_name,
                                          corrector_steps=corrector_steps, predictor=predictor_name,
                                          probability_flow=False, denoise=denoise, noise=noise, seed=s, use_graph=use_graph,
-                                         affine=affine, snr=snr, streams=streams, corrector_scope=corrector_scope)
+                                         affine=affine, snr=snr, streams=streams, corrector_scope=corrector_scope,
+                                         noise_frames=noise_frames)
             return out, nfe
         return native_pc_sampler
 
@@ -150,7 +161,7 @@ def _adaptive_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol,
 
 
 def _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, method, eps, device, noise, seed, streams, solver_kwargs,
-                        step_control="batch"):
+                        step_control="batch", noise_frames=None):
     """The same solver as ``_adaptive_ode_sampler`` -- scipy's RK45 (Dormand-Prince 5(4)) with its initial-step rule and step control
     over the flattened batch -- as ONE library call (sgmse_ode_sample): state, stage slopes and error estimate stay on the device, the
     host reads one scalar (the error norm) per attempted step.  Nothing here falls back: what the library call cannot do raises.
@@ -184,6 +195,8 @@ def _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, m
     std1 = float(sde._std(torch.ones(1))[0])
     affine_fn = score_fn.score_affine if score_fn.score_affine(torch.ones(1)) is not None else None
     extra = dict(step_control=step_control) if step_control != "batch" else {}
+    if noise_frames is not None:
+        extra["noise_frames"] = noise_frames
 
     def tail(x, yy):      # the extra predictor step of the scipy-driven path (see _adaptive_ode_sampler)
         predictor = ReverseDiffusionPredictor(sde, score_fn, probability_flow=False)
@@ -214,7 +227,8 @@ def _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, m
 
 def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e-5, atol=1e-5, method="RK45", eps=3e-2,
                     device=None, noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, use_graph: bool = True,
-                    streams=None, adaptive: Optional[bool] = None, solver: str = "scipy", step_control: str = "batch", **kwargs):
+                    streams=None, adaptive: Optional[bool] = None, solver: str = "scipy", step_control: str = "batch", noise_frames=None,
+                    **kwargs):
     """Probability-flow sampler (reference sampling/__init__.py:73-143), in two forms.
 
     ``adaptive=True`` -- the reference's own behaviour: scipy's black-box solver (``method``, ``rtol``, ``atol``, extra keyword
@@ -222,7 +236,7 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
     call; returns ``(sample, solver NFE)``.  It ignores ``sde.N`` like the reference.  ``solver="native"`` runs the same algorithm
     (RK45 with scipy's step control, one error norm over the whole batch) as one HIP library call without host round trips: it needs an
     OUVESDE, a ScoreModel on a HIP backbone and ``method="RK45"``, takes ``first_step`` / ``max_step`` of solve_ivp's keywords, and
-    ``seed`` / ``streams`` / ``noise`` / ``z`` all apply; anything else raises ValueError.  The returned callable takes ``max_nfe``.
+    ``seed`` / ``streams`` / ``noise_frames`` (see get_pc_sampler) / ``noise`` / ``z`` all apply; anything else raises ValueError.  The returned callable takes ``max_nfe``.
     ``step_control="utterance"`` (native solver only, else ValueError) gives every utterance its own step control instead of the one
     error norm over the batch: an utterance's result no longer depends on what shares its batch (it is, bit for bit, that of its
     single-utterance run), ``y`` may be a ragged list, ``max_nfe`` caps each utterance and the returned nfe is the largest utterance's.
@@ -248,8 +262,9 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
             raise ValueError("solver='native' selects the adaptive solver's implementation: pass adaptive=True (or denoise=False); the fixed-step "
                              "sampler (adaptive=False) always runs in the library")
         return _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, method, eps, device, noise, seed, streams, kwargs,
-                                   step_control)
+                                   step_control, noise_frames)
     if adaptive:
+        _require_native_for_noise_frames(None, noise_frames)
         dropped = [k for k, v in (("seed", seed), ("streams", streams)) if v is not None] + ([] if use_graph else ["use_graph"])
         if dropped:
             warnings.warn(f"get_ode_sampler(adaptive solver): {', '.join(dropped)} do not apply -- scipy's solve_ivp drives one network "
@@ -263,6 +278,7 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
                       f"sampler (N steps, N NFE); pass adaptive=True for the reference's scipy solver")
     ctx = _native_engine(score_fn, y) if isinstance(sde, OUVESDE) else None
     _require_native_for_ragged(ctx, y)
+    _require_native_for_noise_frames(ctx, noise_frames)
     if ctx is None:
         rsde = sde.reverse(score_fn, probability_flow=True)
 
@@ -286,21 +302,24 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
         with torch.no_grad():
             return ctx.pc_sample(y, table, theta=float(sde.theta), std1=std1, corrector="none", corrector_steps=1,
                                  predictor="reverse_diffusion", probability_flow=True, denoise=False, noise=noise, seed=s,
-                                 use_graph=use_graph, affine=affine, streams=streams)
+                                 use_graph=use_graph, affine=affine, streams=streams, noise_frames=noise_frames)
     return ode_sampler
 
 
 def get_sb_sampler(sde, model, y, eps=1e-4, n_steps=50, sampler_type="ode", noise: Optional[torch.Tensor] = None,
-                   seed: Optional[int] = None, use_graph: bool = True, force_python_loop: bool = False, streams=None, **kwargs):
+                   seed: Optional[int] = None, use_graph: bool = True, force_python_loop: bool = False, streams=None, noise_frames=None,
+                   **kwargs):
     """Schroedinger-bridge samplers (reference sampling/__init__.py:145-249): 'ode' (deterministic) and 'sde'.  With a
     ScoreModel on a HIP backbone the N-step loop runs in the library (sgmse_sb_sample); otherwise the reference-style
     Python loop below.  Returns a zero-argument callable -> (sample, n_steps) like the reference.  The library loop also takes a
     ragged list of [F,T_b] / [1,F,T_b] spectrograms (and then ``noise`` as a list of [ndraws,1,F,T_b]) and returns a list of
-    [1,F,T_b], every utterance bit-identical to its own single-utterance call; the Python loop refuses a list."""
+    [1,F,T_b], every utterance bit-identical to its own single-utterance call; the Python loop refuses a list.  ``noise_frames``
+    (library loop, 'sde'): see get_pc_sampler."""
     if sampler_type not in ("ode", "sde"):
         raise ValueError("Invalid type. Choose 'ode' or 'sde'.")
     ctx = None if force_python_loop else (_native_engine(model, y) if isinstance(sde, SBVESDE) else None)
     _require_native_for_ragged(ctx, y)
+    _require_native_for_noise_frames(ctx, noise_frames)
     if ctx is not None:
         table = sde.sb_step_table(eps, sampler_type, sde.N)
         affine = model.score_affine(table["t"])
@@ -310,7 +329,7 @@ def get_sb_sampler(sde, model, y, eps=1e-4, n_steps=50, sampler_type="ode", nois
             with torch.no_grad():
                 y0 = list(y) if isinstance(y, (list, tuple)) else y[:, [0], :, :].contiguous()
                 out, _ = ctx.sb_sample(y0, table, stochastic=(sampler_type == "sde"), noise=noise, seed=s,
-                                       affine=affine, use_graph=use_graph, streams=streams)
+                                       affine=affine, use_graph=use_graph, streams=streams, noise_frames=noise_frames)
             return out, n_steps
         return native_sb_sampler
 

@@ -39,3 +39,18 @@ def window_stream(stream: int, i: int) -> int:
     """Noise-stream id of window i of the recording whose own id is ``stream``: window 0 keeps the recording's id, so a recording
     of one window draws the noise it draws without windows; the window index goes into the id's high word."""
     return (int(stream) + (int(i) << 32)) & (2 ** 64 - 1)
+
+
+WINDOW_NOISE = ("window", "recording")
+
+
+def window_noise_plan(stream: int, starts: List[int], K: int, window_noise: str):
+    """(stream ids, noise geometry) of the windows starting at ``starts`` of a recording of K frames whose id is ``stream``.
+    'window': window i draws from ``window_stream(stream, i)`` at the index inside the window (geometry None: the default).
+    'recording': every window draws from the recording's own id at the index of the recording's frame -- geometry (starts[i], K),
+    ``Context.set_noise_frames`` -- so the windows over a frame share its draws."""
+    if window_noise not in WINDOW_NOISE:
+        raise ValueError(f"window_noise must be 'window' or 'recording', got {window_noise!r}")
+    if window_noise == "recording":
+        return [window_stream(stream, 0)] * len(starts), [(int(a), int(K)) for a in starts]
+    return [window_stream(stream, i) for i in range(len(starts))], None
