@@ -26,6 +26,10 @@
 //   * staging: a lane holds an ALIGNED column quad (x0 - 4 + 4 j .. + 3), j = 0..9, of 4 channels (one 16-byte load per channel); 10
 //     lanes = one (4-channel group, tile row), 6 such rows per wave pass, one pass per wave.  The transform needs the last column of
 //     lane - 1 and the first of lane + 1: the same two whole-wave DPP shifts per channel as F(2,3).  The width must be a multiple of 4.
+//     In the K loop the item of the NEXT stage is cut into 56 units of whole elements (Wino43Units below) that sit BETWEEN the MFMAs
+//     of the first STG taps of a stage (A-waves) or of its last STG taps (B-waves): MFMA, units, MFMA, units, ...  Measured
+//     (DESIGN.md section 8, round 13): the gaps hide little of the item; the form is 1.2-1.6 % faster per launch than two halves
+//     behind the MFMAs of two taps through shorter waits at the stage barriers and 7 % fewer vector instructions.
 //   * A operand: [co block][stage][dy 3][k 6][split 2][cf 4][lane 64] fragments (18 pairs per stage), ring of three, two taps ahead.
 //   * epilogue: A-waves form {M0 + (M1 + M2), M1 - M2, M1 + M2}, B-waves {s, 2 t, 4 s, 8 t + M5} (s = M3 + M4, t = M3 - M4); the
 //     partners swap half through LDS behind one barrier, the A-wave finishes rows 0-3 and the B-wave rows 4-7 (4-row shape: the A-wave
@@ -35,8 +39,53 @@
 //   * no folded shortcut: the 1x1 shortcut runs as its own launch (conv1x1_split_kernel) and arrives here as the residual.
 #pragma once
 #include "kernels_conv_wino.h"
+#include <utility>
+
+// Taps of a K-stage over which a wave spreads the staging of the next stage's item (2: the item in two halves BEHIND the MFMAs of a
+// fragment slot, the placement up to round 12; 3, 4: in units between the MFMAs).  One value per library; the others are for A/B runs of
+// a measurement build (HIPCC_COMPILE_FLAGS_APPEND=-DSGMSE_WINO43_STG=2 make ABLATION=1).  The LDS image does not depend on it.
+#ifndef SGMSE_WINO43_STG
+#define SGMSE_WINO43_STG 3
+#endif
 
 namespace sgmse {
+
+template <class F, int... I>
+__device__ __forceinline__ void wino43_unroll(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void wino43_unroll(F&& f) { wino43_unroll(f, std::make_integer_sequence<int, N>{}); }    // f(0_c) ... f((N-1)_c)
+
+// The staging item of one thread (4 channels x an aligned column quad -> 6 transformed values per channel -> fp16 hi/lo pairs -> 12
+// 8-byte LDS stores) as 56 units in dependency order, each a few instructions of whole elements:
+//   channel c (11 units): E0 E1 F0 F1 E2 E3 F2 F3 Ta Tb Tc    E = affine (+ the exponential of SiLU) of one element, F = its reciprocal,
+//                                                             product and mask; Ta, Tb, Tc = the transform {V1 V2}, {V0 V3 V4}, {V5}
+//   item: channel 0, channel 1, S0(k = 0..5), channel 2, channel 3, S1(k = 0..5)
+//                                                             S0 = hi/lo split of channels 0,1 of component k (kept in registers),
+//                                                             S1 = split of channels 2,3 + the two 8-byte stores of component k
+// cost() = issue cycles (transcendental 8, other VALU 4, LDS store 4 + the exec mask around the pair); gap() deals the units out over
+// the G = 3 NF STG MFMA gaps of the staging taps in proportion to it, in order.
+template <int ACT>
+struct Wino43Units {
+  static constexpr int NCH = 11, NU = 4 * NCH + 12;
+  enum Kind { E, F, TA, TB, TC, S0, S1 };
+  static constexpr bool in_chan(int u) { return u < 2 * NCH || (u >= 2 * NCH + 6 && u < 4 * NCH + 6); }
+  static constexpr int chan_pos(int u) { return u < 2 * NCH ? u : u - 6; }                    // (channel units only)
+  static constexpr int chan(int u) { return chan_pos(u) / NCH; }
+  static constexpr int first_unit(int c) { return c < 2 ? c * NCH : c * NCH + 6; }
+  static constexpr Kind kind(int u) {
+    if (!in_chan(u)) return u < 2 * NCH + 6 ? S0 : S1;
+    const int j = chan_pos(u) % NCH;
+    return j >= 8 ? (j == 8 ? TA : j == 9 ? TB : TC) : (j & 2) ? F : E;
+  }
+  static constexpr int elem(int u) { const int j = chan_pos(u) % NCH; return (j & 1) + 2 * (j >> 2); }      // (E, F)
+  static constexpr int comp(int u) { return u < 2 * NCH + 6 ? u - 2 * NCH : u - (4 * NCH + 6); }            // (S0, S1)
+  static constexpr int cost(int u) {
+    const Kind k = kind(u);
+    return k == E ? (ACT ? 16 : 4) : k == F ? (ACT ? 20 : 4) : k == TA ? 24 : k == TB ? 20 : k == TC ? 12 : k == S0 ? 16 : 28;
+  }
+  static constexpr int before(int u) { int s = 0; for (int i = 0; i < u; ++i) s += cost(i); return s; }
+  static constexpr int gap(int u, int G) { return (2 * before(u) + cost(u)) * G / (2 * before(NU)); }         // monotone in u, < G
+};
 
 template <int ROWS_>
 struct Wino43Geom {
@@ -276,37 +325,139 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino43_kernel(ConvArgs p) {
   // B fragment base of this lane: position (row 4 f + (l31 >> 3) [+ dy], quad l31 & 7), k-group kg
   const int b_lane = l31 * PV + kg * NS;
 
-  // one tap = component k of kernel row dy: NF position fragments x 3 split products; behind each fragment's MFMAs a share of the
-  // staging work of the next stage's item: phase 0 = channels 0-1, phase 1 = channels 2-3 and the LDS writes (-1: none)
+  // one unit of the next stage's item (Wino43Units): the expressions of produce_co, stage_chan_co and flush_item, element by element
+  using U = Wino43Units<ACT>;
+  constexpr int STG = SGMSE_WINO43_STG, NGAP = 3 * NF * STG;
+  static_assert(STG >= 2 && 2 * STG < 9, "the two waves of a SIMD never stage in the same tap");
+  struct Item {                // (every field is written once per stage, by one unit, before the units that read it)
+    f32x4 co[4];
+    float o[4][4], e[4][4], d[4][4], a[4], bb[4];     // an element between E and F; d1..d4 of a channel; a, bb of its transform
+    float V[6][4];
+    uint32_t h[6][2];                                 // hi / lo halves of channels 0,1 until channels 2,3 are there
+  };
+  // The units sit in conditional blocks (a wave stages or does not) and hand their values on through an Item.  At the join behind a
+  // block the value "from the other side" has to be SOMETHING: an uninitialised variable becomes a zero the compiler materialises on
+  // the path every wave runs (one v_mov per value), a variable that lives across stages a register held around the whole loop.
+  // fresh() in front of the block gives the variable a register and no instruction; the block then writes into that register.
+  auto fresh = [&](auto& x) __attribute__((always_inline)) {
+#ifndef SGMSE_EMULATOR
+    asm volatile("" : "=v"(x));
+#else
+    (void)x;
+#endif
+  };
+  auto fresh_outputs = [&](auto u_c, Item& it) __attribute__((always_inline)) {
+    constexpr int u = decltype(u_c)::value;
+    constexpr auto kind = U::kind(u);
+    if constexpr (kind == U::E) { fresh(it.o[U::chan(u)][U::elem(u)]); if constexpr (ACT == 1) fresh(it.e[U::chan(u)][U::elem(u)]); }
+    else if constexpr (kind == U::F) fresh(it.d[U::chan(u)][U::elem(u)]);
+    else if constexpr (kind == U::TA) { fresh(it.a[U::chan(u)]); fresh(it.bb[U::chan(u)]); fresh(it.V[1][U::chan(u)]); fresh(it.V[2][U::chan(u)]); }
+    else if constexpr (kind == U::TB) { fresh(it.V[0][U::chan(u)]); fresh(it.V[3][U::chan(u)]); fresh(it.V[4][U::chan(u)]); }
+    else if constexpr (kind == U::TC) fresh(it.V[5][U::chan(u)]);
+    else if constexpr (kind == U::S0) { fresh(it.h[U::comp(u)][0]); fresh(it.h[U::comp(u)][1]); }
+  };
+  auto unit = [&](auto u_c, Item& it, u32x4* nxt) __attribute__((always_inline)) {
+    constexpr int u = decltype(u_c)::value;
+    constexpr auto kind = U::kind(u);
+    if constexpr (kind == U::E) {
+      constexpr int c = U::chan(u), e = U::elem(u);
+      it.o[c][e] = rin[4 * c + e] * it.co[c][0] + it.co[c][1];
+      if constexpr (ACT == 1) it.e[c][e] = drt_exp2(rin[4 * c + e] * it.co[c][2] + it.co[c][3]);
+    } else if constexpr (kind == U::F) {
+      constexpr int c = U::chan(u), e = U::elem(u);
+      float o = it.o[c][e];
+      if constexpr (ACT == 1) o = o * __builtin_amdgcn_rcpf(1.0f + it.e[c][e]);
+      it.d[c][e] = it_ok ? o : 0.f;
+    } else if constexpr (kind == U::TA) {
+      constexpr int c = U::chan(u);
+      it.a[c] = it.d[c][3] - it.d[c][1]; it.bb[c] = it.d[c][2] - it.d[c][0];
+      const float c4 = it.d[c][3] - 4.f * it.d[c][1], c3 = it.d[c][2] - 4.f * it.d[c][0];
+      it.V[1][c] = c4 + c3;
+      it.V[2][c] = c4 - c3;
+    } else if constexpr (kind == U::TB) {
+      constexpr int c = U::chan(u);
+      const float d0 = drt_wave_shr1(it.d[c][3]);
+      it.V[0][c] = 4.f * (d0 - it.d[c][1]) + it.a[c];
+      it.V[3][c] = it.a[c] + 2.f * it.bb[c];
+      it.V[4][c] = it.a[c] - 2.f * it.bb[c];
+    } else if constexpr (kind == U::TC) {
+      constexpr int c = U::chan(u);
+      const float d5 = drt_wave_shl1(it.d[c][0]);
+      it.V[5][c] = (d5 - it.d[c][2]) - 4.f * it.bb[c];
+    } else if constexpr (kind == U::S0) {
+      constexpr int k = U::comp(u);
+      S::split2(it.V[k][0], it.V[k][1], it.h[k]);
+    } else {
+      constexpr int k = U::comp(u);
+      uint32_t d23[2];
+      S::split2(it.V[k][2], it.V[k][3], d23);
+      if (it_wr) {
+        uint2* w = reinterpret_cast<uint2*>(nxt) + it_woff;
+        w[k * 8] = make_uint2(it.h[k][0], d23[0]);
+        w[k * 8 + 2] = make_uint2(it.h[k][1], d23[1]);
+      }
+    }
+  };
+
+  // one tap = component k of kernel row dy: NF position fragments x 3 split products.  SLOT >= 0: the SLOT-th of this wave's STG staging
+  // taps -- behind each MFMA the units of that gap, in a conditional block of their own (stage_here: this wave stages in this tap), whose
+  // ends also fence them: the scheduler moves nothing across (STG = 2: behind each fragment's three MFMAs half of the item's channels
+  // 2 SLOT, 2 SLOT + 1, and the LDS writes at the end of slot 1)
   u32x4 bq[2][NS];
-  auto compute_tap = [&](const u32x4* sbuf, int tap, const u32x4 (&a)[NS], int phase, bool stage_here, int c0n, u32x4* nxt) {
+  auto compute_tap = [&](auto slot_c, bool stage_here, Item& it, const u32x4* sbuf, int tap, const u32x4 (&a)[NS], int c0n, u32x4* nxt) __attribute__((always_inline)) {
+    constexpr int SLOT = decltype(slot_c)::value;
+    constexpr bool SPREAD = SLOT >= 0 && STG > 2;
     const int dy = tap / 3, kk = tap - 3 * dy;
     const u32x4* sb = sbuf + b_lane + dy * G::ROW_V + (3 * kh + kk) * 4;
-    f32x4 co2[2];
-    if (phase >= 0 && stage_here) {
+    if constexpr (SPREAD) {
+      wino43_unroll<4>([&](auto c_c) __attribute__((always_inline)) {       // the coefficients of the channels that begin in this tap
+        constexpr int c = decltype(c_c)::value;
+        if constexpr (U::gap(U::first_unit(c), NGAP) / (3 * NF) == SLOT) {
+          fresh(it.co[c]);
+          if (stage_here) it.co[c] = s_co[c0n + 4 * it_q + c];
+        }
+      });
+    } else if constexpr (SLOT >= 0) {
+      if (stage_here) {
 #pragma unroll
-      for (int c = 0; c < 2; ++c) co2[c] = s_co[c0n + 4 * it_q + 2 * phase + c];
+        for (int c = 0; c < 2; ++c) it.co[c] = s_co[c0n + 4 * it_q + 2 * SLOT + c];
+      }
     }
 #pragma unroll
     for (int s = 0; s < NS; ++s) bq[0][s] = sb[s];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      if (f + 1 < NF) {
+    wino43_unroll<NF>([&](auto f_c) __attribute__((always_inline)) {
+      constexpr int f = decltype(f_c)::value;
+      if constexpr (f + 1 < NF) {
         const u32x4* q = sb + (f + 1) * 4 * G::ROW_V;
 #pragma unroll
         for (int s = 0; s < NS; ++s) bq[(f + 1) & 1][s] = q[s];
       }
       __builtin_amdgcn_sched_barrier(SGMSE_SPLIT_FENCE);
+      wino43_unroll<S::NP>([&](auto k_c) __attribute__((always_inline)) {
+        constexpr int k = decltype(k_c)::value;
+        acc[kk][f] = S::mfma(a[S::pa(k)], bq[f & 1][S::pb(k)], acc[kk][f]);
+        if constexpr (SPREAD) {
+          constexpr int gap = (SLOT * NF + f) * S::NP + k;
+          wino43_unroll<U::NU>([&](auto u_c) __attribute__((always_inline)) {
+            if constexpr (U::gap(decltype(u_c)::value, NGAP) == gap) fresh_outputs(u_c, it);
+          });
+          if (stage_here) {
+            wino43_unroll<U::NU>([&](auto u_c) __attribute__((always_inline)) {
+              if constexpr (U::gap(decltype(u_c)::value, NGAP) == gap) unit(u_c, it, nxt);
+            });
+          }
+        }
+      });
+      if constexpr (SLOT >= 0 && !SPREAD) {
+        if (stage_here) {
+          constexpr int CPF = 2 / NF;                 // channels per fragment slot (1 for 8 rows, 2 for 4)
 #pragma unroll
-      for (int k = 0; k < S::NP; ++k) acc[kk][f] = S::mfma(a[S::pa(k)], bq[f & 1][S::pb(k)], acc[kk][f]);
-      if (phase >= 0 && stage_here) {
-        constexpr int CPF = 2 / NF;                   // channels per fragment slot (1 for 8 rows, 2 for 4)
-#pragma unroll
-        for (int c = 0; c < CPF; ++c) stage_chan_co(2 * phase + f * CPF + c, co2[f * CPF + c]);
-        if (phase == 1 && f == NF - 1) flush_item(nxt);
+          for (int c = 0; c < CPF; ++c) stage_chan_co(2 * SLOT + f * CPF + c, it.co[f * CPF + c]);
+          if (SLOT == 1 && f == NF - 1) flush_item(nxt);
+        }
       }
       __builtin_amdgcn_sched_barrier(SGMSE_SPLIT_FENCE);
-    }
+    });
   };
 
   __syncthreads();          // s_co visible
@@ -331,24 +482,27 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino43_kernel(ConvArgs p) {
     const int stl = st + 2 < nst ? st + 2 : nst - 1;
     const u32x4* cur = (st & 1) ? s_in1 : s_in0;
     u32x4* nxt = (st & 1) ? s_in0 : s_in1;
-#pragma unroll
-    for (int tap = 0; tap < NTAP; ++tap) {
+    // staging of the next stage's item: the A-waves in the FIRST STG taps, the B-waves in the LAST STG (the two waves of a SIMD are
+    // (cf, 0) and (cf, 1): de-phased, one wave's producer arithmetic issues beside the other's MFMAs); the last stage stages nothing
+    // and the last two load nothing.  The raw inputs two stages ahead are fetched behind the last unit that reads rin.
+    // (one item per role, declared here: its registers are live over that role's staging taps only)
+    const bool stage_a = it_run && kh == 0 && st + 1 < nst, stage_b = it_run && kh == 1 && st + 1 < nst;
+    Item item_a, item_b;
+    wino43_unroll<NTAP>([&](auto tap_c) __attribute__((always_inline)) {
+      constexpr int tap = decltype(tap_c)::value;
       unsigned long long tc0 = 0;
       if constexpr (TRACE) tc0 = drt_clock();
-      const int ntap = (tap + AD) % NTAP;
+      constexpr int ntap = (tap + AD) % NTAP;
       const int nstg = tap + AD < NTAP ? st : stn;
       load_a(nstg, ntap, ar[(tap + AD) % AR]);        // issued before the raw loads below: vmcnt retires in order
       __builtin_amdgcn_sched_barrier(0);
-      // staging of the next stage's item: the A-waves in the FIRST two taps, the B-waves in the LAST two (the two waves of a SIMD are
-      // (cf, 0) and (cf, 1): de-phased, one wave's producer arithmetic issues beside the other's MFMAs); the last stage stages nothing
-      // and the last two load nothing
-      const bool ca = tap < 2, cb = tap >= NTAP - 2;
-      const int phase = ca ? tap : cb ? tap - (NTAP - 2) : -1;
-      const bool stage_here = phase >= 0 && it_run && (ca ? kh == 0 : kh == 1) && st + 1 < nst;
-      compute_tap(cur, tap, ar[tap % AR], phase, stage_here, stn * G::KC, nxt);
-      if (phase == 1 && stage_here && st + 2 < nst) load_item(stl * G::KC);
+      constexpr bool ca = tap < STG;
+      constexpr int slot = ca ? tap : tap >= NTAP - STG ? tap - (NTAP - STG) : -1;
+      const bool stage_here = slot >= 0 && (ca ? stage_a : stage_b);
+      compute_tap(std::integral_constant<int, slot>{}, stage_here, ca ? item_a : item_b, cur, tap, ar[tap % AR], stn * G::KC, nxt);
+      if (slot == STG - 1 && stage_here && st + 2 < nst) load_item(stl * G::KC);
       if constexpr (TRACE) { __builtin_amdgcn_sched_barrier(0); ttap[tap] += drt_clock() - tc0; }
-    }
+    });
     if constexpr (TRACE) {
       const unsigned long long tb = drt_clock();
       __syncthreads();
