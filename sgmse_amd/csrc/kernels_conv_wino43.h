@@ -47,6 +47,18 @@
 #ifndef SGMSE_WINO43_STG
 #define SGMSE_WINO43_STG 3
 #endif
+// How the K loop's MFMAs get their operands, a bit mask (one value per library; 0 = the instruction order up to round 13, for A/B runs
+// of one source as above).  No bit changes a value or an address, only when a load or read is issued:
+//   1  B fragments one fragment slot ahead: fragment 0 of tap t + 1 is read from LDS in front of the MFMAs of the last fragment of
+//      tap t; only the first fragment of a stage is read at the top of its tap, behind the stage barrier
+//   2  A fragments through a raw buffer view of the weight block: per-lane offset in one register computed before the loop, (stage,
+//      dy, k, split) in the scalar offset -- no address arithmetic on the vector ALU in the loop
+//   4  (reserved: exact vmcnt waits behind a wave's raw look-ahead loads; not built)
+//   8  the first two taps of the weight ring are loaded beside the other prologue loads, in front of the staging of item 0
+// 3 ships.  Bit 8 measured inside the run-to-run spread on the headline and stays off.
+#ifndef SGMSE_WINO43_FEED
+#define SGMSE_WINO43_FEED 3
+#endif
 
 namespace sgmse {
 
@@ -167,6 +179,14 @@ __global__ __launch_bounds__(256) void pack_weights_wino43_kernel(PackWinoArgs p
   }
   reinterpret_cast<u32x4*>(p.dst)[e] = o;
 }
+
+// One 16-byte A fragment element through a raw buffer view (SGMSE_WINO43_FEED bit 2): drt_buf_load4 of sgmse_devrt.h; the CPU
+// emulator's form of it lives here, next to its only use
+#ifndef SGMSE_EMULATOR
+__device__ __forceinline__ u32x4 wino43_buf_load4(const drt_buf& b, unsigned voff, unsigned soff) { return drt_buf_load4(b, voff, soff); }
+#else
+static inline u32x4 wino43_buf_load4(const drt_buf& b, unsigned voff, unsigned soff) { u32x4 v; memcpy(&v, b.p + voff + soff, 16); return v; }
+#endif
 
 // ACT: SiLU behind the GroupNorm affine of the fused producer (1) or the affine only (0).
 // TRACE (measurement only, sgmse_bench_conv in an ABLATION build): phase time stamps per workgroup, 32 words as conv3x3_wino_kernel's
@@ -316,11 +336,22 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino43_kernel(ConvArgs p) {
   // A fragments of this wave: tap (dy, kk) of stage st -> [st][dy][3 kh + kk][split][cf][lane]
   const u32x4* wblk = reinterpret_cast<const u32x4*>(p.w) + (size_t)co_blk * nst * 18 * NS * 4 * 64;
   const unsigned a_boff = (unsigned)((cf * 64 + lane) * 16);
+  constexpr int FEED = SGMSE_WINO43_FEED;
+  constexpr bool B_AHEAD = (FEED & 1) != 0, A_BUF = (FEED & 2) != 0, A_EARLY = (FEED & 8) != 0;
+  static_assert((FEED & ~11) == 0, "SGMSE_WINO43_FEED: bits 1, 2 and 8");
+  // (A_BUF: a co block's fragments end below nst * 18 * NS * 4 * 64 * 16 bytes = 4.5 MB at 512 input channels, far below the view's 2^31)
+  const drt_buf wbuf = drt_make_buf(reinterpret_cast<const float*>(wblk));
   auto load_a = [&](int st, int tap, u32x4 (&a)[NS]) {
     const int dy = tap / 3, k = 3 * kh + (tap - 3 * dy);
-    const u32x4* q = wblk + (size_t)((st * 3 + dy) * 6 + k) * NS * 4 * 64;
+    if constexpr (A_BUF) {
+      const unsigned soff = (unsigned)((st * 3 + dy) * 6 + k) * (unsigned)(NS * 4 * 64 * 16);
 #pragma unroll
-    for (int s = 0; s < NS; ++s) a[s] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(q + s * 4 * 64) + a_boff);
+      for (int s = 0; s < NS; ++s) a[s] = wino43_buf_load4(wbuf, a_boff, soff + (unsigned)(s * 4 * 64 * 16));
+    } else {
+      const u32x4* q = wblk + (size_t)((st * 3 + dy) * 6 + k) * NS * 4 * 64;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) a[s] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(q + s * 4 * 64) + a_boff);
+    }
   };
   // B fragment base of this lane: position (row 4 f + (l31 >> 3) [+ dy], quad l31 & 7), k-group kg
   const int b_lane = l31 * PV + kg * NS;
@@ -403,11 +434,23 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino43_kernel(ConvArgs p) {
   // taps -- behind each MFMA the units of that gap, in a conditional block of their own (stage_here: this wave stages in this tap), whose
   // ends also fence them: the scheduler moves nothing across (STG = 2: behind each fragment's three MFMAs half of the item's channels
   // 2 SLOT, 2 SLOT + 1, and the LDS writes at the end of slot 1)
+  // B_AHEAD: a fragment is read one fragment slot ahead of its MFMAs, across taps too -- fragment 0 of tap t + 1 in front of the MFMAs
+  // of the last fragment of tap t; read_b(., 0, 0) behind the stage barrier (the other buffer is written until then), tap 8 reads
+  // nothing ahead.  Slot of (tap, f) in bq: f at NF = 2, tap & 1 at NF = 1 (tap 8 and the next stage's tap 0 both 0: that read sits
+  // behind tap 8's MFMAs and the barrier)
   u32x4 bq[2][NS];
-  auto compute_tap = [&](auto slot_c, bool stage_here, Item& it, const u32x4* sbuf, int tap, const u32x4 (&a)[NS], int c0n, u32x4* nxt) __attribute__((always_inline)) {
+  auto read_b = [&](const u32x4* sbuf, auto tap_c, auto f_c) __attribute__((always_inline)) {
+    constexpr int tap = decltype(tap_c)::value, f = decltype(f_c)::value;
+    constexpr int dy = tap / 3, kk = tap - 3 * dy, slot = NF > 1 ? (f & 1) : (tap & 1);
+    const u32x4* q = sbuf + b_lane + dy * G::ROW_V + (3 * kh + kk) * 4 + f * 4 * G::ROW_V;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) bq[slot][s] = q[s];
+  };
+  auto compute_tap = [&](auto slot_c, auto tap_c, bool stage_here, Item& it, const u32x4* sbuf, const u32x4 (&a)[NS], int c0n, u32x4* nxt) __attribute__((always_inline)) {
     constexpr int SLOT = decltype(slot_c)::value;
+    constexpr int tap = decltype(tap_c)::value;
     constexpr bool SPREAD = SLOT >= 0 && STG > 2;
-    const int dy = tap / 3, kk = tap - 3 * dy;
+    constexpr int dy = tap / 3, kk = tap - 3 * dy;
     const u32x4* sb = sbuf + b_lane + dy * G::ROW_V + (3 * kh + kk) * 4;
     if constexpr (SPREAD) {
       wino43_unroll<4>([&](auto c_c) __attribute__((always_inline)) {       // the coefficients of the channels that begin in this tap
@@ -423,19 +466,28 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino43_kernel(ConvArgs p) {
         for (int c = 0; c < 2; ++c) it.co[c] = s_co[c0n + 4 * it_q + 2 * SLOT + c];
       }
     }
+    if constexpr (!B_AHEAD) {
 #pragma unroll
-    for (int s = 0; s < NS; ++s) bq[0][s] = sb[s];
+      for (int s = 0; s < NS; ++s) bq[0][s] = sb[s];
+    }
     wino43_unroll<NF>([&](auto f_c) __attribute__((always_inline)) {
       constexpr int f = decltype(f_c)::value;
+      constexpr int bs = B_AHEAD && NF == 1 ? (tap & 1) : (f & 1);
       if constexpr (f + 1 < NF) {
-        const u32x4* q = sb + (f + 1) * 4 * G::ROW_V;
+        if constexpr (B_AHEAD) {
+          read_b(sbuf, tap_c, std::integral_constant<int, f + 1>{});
+        } else {
+          const u32x4* q = sb + (f + 1) * 4 * G::ROW_V;
 #pragma unroll
-        for (int s = 0; s < NS; ++s) bq[(f + 1) & 1][s] = q[s];
+          for (int s = 0; s < NS; ++s) bq[(f + 1) & 1][s] = q[s];
+        }
+      } else if constexpr (B_AHEAD && tap + 1 < 9) {
+        read_b(sbuf, std::integral_constant<int, tap + 1>{}, std::integral_constant<int, 0>{});
       }
       __builtin_amdgcn_sched_barrier(SGMSE_SPLIT_FENCE);
       wino43_unroll<S::NP>([&](auto k_c) __attribute__((always_inline)) {
         constexpr int k = decltype(k_c)::value;
-        acc[kk][f] = S::mfma(a[S::pa(k)], bq[f & 1][S::pb(k)], acc[kk][f]);
+        acc[kk][f] = S::mfma(a[S::pa(k)], bq[bs][S::pb(k)], acc[kk][f]);
         if constexpr (SPREAD) {
           constexpr int gap = (SLOT * NF + f) * S::NP + k;
           wino43_unroll<U::NU>([&](auto u_c) __attribute__((always_inline)) {
@@ -460,6 +512,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino43_kernel(ConvArgs p) {
     });
   };
 
+  constexpr int AR = 3, AD = AR - 1, NTAP = 9;
+  u32x4 ar[AR][NS];
+  if constexpr (A_EARLY) {  // the ring's first two taps: issued behind item 0's raw loads (vmcnt retires in order), their L2 latency under its staging
+#pragma unroll
+    for (int t = 0; t < AD; ++t) load_a(0, t, ar[t]);
+  }
   __syncthreads();          // s_co visible
   if (it_run) {
 #pragma unroll
@@ -470,12 +528,12 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino43_kernel(ConvArgs p) {
   __syncthreads();
 
   if constexpr (TRACE) { if (trace) trace[2] = drt_clock(); }
-  constexpr int AR = 3, AD = AR - 1, NTAP = 9;
   unsigned long long tbar = 0, ttap[NTAP] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   const bool tracer = TRACE && p.trace && (tid == 0 || tid == 256);       // one lane of an A-wave and of a B-wave time their taps
-  u32x4 ar[AR][NS];
+  if constexpr (!A_EARLY) {
 #pragma unroll
-  for (int t = 0; t < AD; ++t) load_a(0, t, ar[t]);
+    for (int t = 0; t < AD; ++t) load_a(0, t, ar[t]);
+  }
 #pragma unroll 1
   for (int st = 0; st < nst; ++st) {
     const int stn = st + 1 < nst ? st + 1 : st;
@@ -494,12 +552,16 @@ __global__ __launch_bounds__(512, 1) void conv3x3_wino43_kernel(ConvArgs p) {
       if constexpr (TRACE) tc0 = drt_clock();
       constexpr int ntap = (tap + AD) % NTAP;
       const int nstg = tap + AD < NTAP ? st : stn;
+      if constexpr (B_AHEAD && tap == 0) {             // the stage's first fragment: behind the barrier, ahead of the ring's address work
+        read_b(cur, tap_c, std::integral_constant<int, 0>{});
+        __builtin_amdgcn_sched_barrier(0);
+      }
       load_a(nstg, ntap, ar[(tap + AD) % AR]);        // issued before the raw loads below: vmcnt retires in order
       __builtin_amdgcn_sched_barrier(0);
       constexpr bool ca = tap < STG;
       constexpr int slot = ca ? tap : tap >= NTAP - STG ? tap - (NTAP - STG) : -1;
       const bool stage_here = slot >= 0 && (ca ? stage_a : stage_b);
-      compute_tap(std::integral_constant<int, slot>{}, stage_here, ca ? item_a : item_b, cur, tap, ar[tap % AR], stn * G::KC, nxt);
+      compute_tap(std::integral_constant<int, slot>{}, tap_c, stage_here, ca ? item_a : item_b, cur, ar[tap % AR], stn * G::KC, nxt);
       if (slot == STG - 1 && stage_here && st + 2 < nst) load_item(stl * G::KC);
       if constexpr (TRACE) { __builtin_amdgcn_sched_barrier(0); ttap[tap] += drt_clock() - tc0; }
     });

@@ -82,6 +82,11 @@ __device__ __forceinline__ void drt_buf_store2(const drt_buf& b, float2 v, unsig
   const u2_t u = {__builtin_bit_cast(unsigned, v.x), __builtin_bit_cast(unsigned, v.y)};
   __builtin_amdgcn_raw_buffer_store_b64(u, b.r, voff, soff, AUX);
 }
+// 16 bytes (16-byte aligned) as four dwords: buffer_load_dwordx4
+template <int AUX = 0>
+__device__ __forceinline__ u32x4 drt_buf_load4(const drt_buf& b, unsigned voff, unsigned soff) {
+  return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(b.r, voff, soff, AUX));
+}
 // measurement: shader clock and the hardware placement of this wave (HW_REG_HW_ID, HW_REG_XCC_ID)
 __device__ __forceinline__ unsigned long long drt_clock() { return __builtin_amdgcn_s_memtime(); }
 __device__ __forceinline__ unsigned drt_hw_id() { return __builtin_amdgcn_s_getreg((31 << 11) | 4); }
