@@ -200,6 +200,37 @@ int sgmse_spec_split(sgmse_ctx* ctx, const void* spec, void* windows, int F, int
 int sgmse_spec_merge(sgmse_ctx* ctx, const void* windows, void* spec, int F, int K, const int* start, const int* frames, int n,
                      int transform_type, float factor, float exponent);
 
+/* -- one reverse process over a long recording, only the network windowed (not in the reference) ------------------------------
+ * A UNIFORM plan is n windows of exactly W frames, window j = frames [start[j], start[j] + W) of a recording of K frames; start is a
+ * HOST array of length n.  All three calls return SGMSE_EINVAL (message in sgmse_last_error) unless start[0] = 0, the starts strictly
+ * increase, every window lies inside [0, K), the windows cover [0, K) without a gap and no frame lies under four windows (a frame
+ * may lie under three).  The window layout is complex64 [n][F][W], frames fastest.
+ * gather: windows[j][f][t] = src[f][start[j] + t] for src complex64 [F][K]: a plain copy, no spectrogram transform. */
+int sgmse_window_gather(sgmse_ctx* ctx, const void* src, void* windows, int F, int K, int W, const int* start, int n);
+/* blend: dst[f][k] (complex64 [F][K]) from the windows over frame k.  Window j has the local frame t = k - start[j] and the weight
+ *    w_j = min(1, up, down): up = ((float)t + 0.5f) / (float)L_j for j > 0, L_j = start[j-1] + W - start[j] (its overlap with its
+ *    predecessor); down = ((float)(W - t) - 0.5f) / (float)L_{j+1} for j < n - 1.  With a the value of the first window over k and
+ *    S the sum of the weights (ascending j), each real component is out = a, then out = fmaf(w_j / S, v_j - a, out) for every later
+ *    window over k.  So a frame under one window is that window's element bit for bit, windows that agree give their common value
+ *    bit for bit, and two neighbours whose overlap has the length of both their other overlaps get sgmse_spec_merge's cross-fade
+ *    (without its spec_back).  IEEE division and fma, one thread per output element, no atomics. */
+int sgmse_window_blend(sgmse_ctx* ctx, const void* windows, void* dst, int F, int K, int W, const int* start, int n);
+/* The plan for ALL FOLLOWING sgmse_pc_sample / sgmse_sb_sample calls, until the next call (n = 0 withdraws it).  Those calls then take
+ * ONE recording, B = 1 and T = K (K need not be a multiple of 2^(levels-1); W must be), and run ONE reverse process on it: state,
+ * noise and every sampler update are the recording's, [F][K] -- the in-kernel noise is the recording's own field, index f * K + t,
+ * and replayed noise is [ndraws][F][K] --; only the network is windowed.  Each score evaluation gathers the current state's windows,
+ * runs the network on them in C = ceil(n / max_batch) chunks of Bc = ceil(n / C) windows (y's windows are gathered once per call)
+ * and blends the windows' scores (sgmse_window_blend) into the recording's score.  The up to C - 1 empty slots of the last chunk
+ * evaluate its last window again; their scores are not blended.  So the network runs at one shape, the whole step is one captured
+ * graph (a second recording of the same K and plan does not capture again), and -- a window's score depending on its own frames
+ * only -- the result does not depend on max_batch.  Memory: 4 * 8 F K bytes of state, (2 C Bc + Bc) * 8 F W bytes of window buffers
+ * (C Bc < n + C) and the activation arena of Bc windows.
+ * The sampler call returns SGMSE_EINVAL with a plan in force if B != 1 or T != K, in a ragged context (sgmse_set_frames) and with a
+ * pending noise geometry (sgmse_set_noise_frames); sgmse_set_windows itself for a bad plan, max_batch < 1 and W not a multiple of
+ * 2^(levels-1).  sgmse_ode_sample / sgmse_ode_sample_each with a plan in force: SGMSE_EINVAL, "not supported" (the adaptive
+ * solver's error norm and step control are not built for it).  Unmeasured: quality -- no trained checkpoint exists here. */
+int sgmse_set_windows(sgmse_ctx* ctx, int K, int W, const int* start, int n, int max_batch);
+
 /* -- upfirdn2d(input, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad_y1)
  *    (op/upfirdn2d.cpp:12-23, op/upfirdn2d_kernel.cu:209-369).  input fp32 [BC][H][W], kernel fp32 [kh][kw],
  *    out fp32 [BC][(H*up_y+pad_y0+pad_y1-kh)/down_y+1][(W*up_x+pad_x0+pad_x1-kw)/down_x+1]. */

@@ -8,6 +8,7 @@ reports a different ``backend`` string and is never loaded implicitly.)
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import threading
@@ -93,6 +94,9 @@ _SIGS = {
     "sgmse_set_noise_streams": (_I, [_P, C.POINTER(C.c_ulonglong), _I]),
     "sgmse_set_noise_frames": (_I, [_P, C.POINTER(_I), C.POINTER(_I), _I]),
     "sgmse_set_frames": (_I, [_P, C.POINTER(_I), _I]),
+    "sgmse_set_windows": (_I, [_P, _I, _I, C.POINTER(_I), _I, _I]),
+    "sgmse_window_gather": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(_I), _I]),
+    "sgmse_window_blend": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(_I), _I]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -210,6 +214,7 @@ class Context:
         self._keep: Dict[str, object] = {}
         self._frames: list = []          # frame table in force in the library (set_frames); [] = uniform batches
         self._noise_frames_pending = False      # a noise geometry handed to the library that no sampler call has consumed yet
+        self._windows = None             # window plan in force in the library (set_windows); None = none
 
     def __del__(self):
         try:
@@ -362,12 +367,14 @@ class Context:
     def pc_sample(self, Y: torch.Tensor, table: Dict[str, torch.Tensor], *, theta: float, std1: float,
                   corrector: str, corrector_steps: int, predictor: str, probability_flow: bool, denoise: bool,
                   noise: Optional[torch.Tensor], seed: int, use_graph: bool = True, affine=None, snr: float = 0.0, streams=None,
-                  corrector_scope: str = "batch", noise_frames=None):
+                  corrector_scope: str = "batch", noise_frames=None, windows=None, window_batch=None):
         """``affine``: optional (in_scale, score_alpha, score_beta) fp32 tensors of length N: the score wrapper of
         ScoreModel.forward's new-code branch (ncsnpp_v2); None = old-code branch (score = -F).  ``corrector_scope``: 'batch' --
         the 'langevin' corrector takes its step size from the batch-mean norms (the reference) -- or 'utterance': from each
         utterance's own norms, what that utterance gets in a batch of its own (uniform and ragged batches).  ``noise`` of a ragged
-        batch: a list of [ndraws,1,F,T_b] tensors, one per utterance.  ``noise_frames``: see set_noise_frames."""
+        batch: a list of [ndraws,1,F,T_b] tensors, one per utterance.  ``noise_frames``: see set_noise_frames.  ``windows`` = (W, starts),
+        ``window_batch``: the call runs under that window plan (set_windows: one recording [1,1,F,K], K = starts[-1] + W, one reverse
+        process, the network on up to ``window_batch`` windows at a time); the plan is withdrawn when the call returns."""
         if corrector_scope not in ("batch", "utterance"):
             raise ValueError(f"corrector_scope must be 'batch' or 'utterance', got {corrector_scope!r}")
         frames = None
@@ -419,8 +426,9 @@ class Context:
             # the frame table stays in force between calls: consecutive ragged batches of one composition re-use the arena plan
             # and the captured graph; a uniform call switches it off
             self.set_frames(frames if frames is not None else [])
-            self.check(self.lib.sgmse_pc_sample(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, C.byref(cfg), ptr(noise),
-                                                C.c_ulonglong(seed & (2 ** 64 - 1)), C.byref(nfe)))
+            with self._windows_for_call(windows, window_batch):
+                self.check(self.lib.sgmse_pc_sample(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, C.byref(cfg), ptr(noise),
+                                                    C.c_ulonglong(seed & (2 ** 64 - 1)), C.byref(nfe)))
             self._noise_frames_pending = False
 
         self._with_capturable_stream(run, use_graph)
@@ -428,10 +436,10 @@ class Context:
         return (out if frames is None else _unpack_ragged(out, frames, F_)), nfe.value
 
     def sb_sample(self, Y: torch.Tensor, table: Dict[str, torch.Tensor], *, stochastic: bool, noise: Optional[torch.Tensor],
-                  seed: int, affine=None, use_graph: bool = True, streams=None, noise_frames=None):
+                  seed: int, affine=None, use_graph: bool = True, streams=None, noise_frames=None, windows=None, window_batch=None):
         """Schroedinger-bridge sampler; table: fp32 tensors t, w_prev, w_est, w_y, w_z of length N.  ``Y``: [B,1,F,T], or a ragged list
         of [F,T_b] / [1,F,T_b] spectrograms (``set_frames``; the samples come back as a list of [1,F,T_b], ``noise`` is then a list of
-        [ndraws,1,F,T_b] tensors).  ``noise_frames``: see set_noise_frames."""
+        [ndraws,1,F,T_b] tensors).  ``noise_frames``: see set_noise_frames.  ``windows``, ``window_batch``: see pc_sample."""
         frames = None
         if isinstance(Y, (list, tuple)):
             B = len(Y)
@@ -460,9 +468,10 @@ class Context:
         def run():
             self.use_current_stream()
             self.set_frames(frames if frames is not None else [])
-            self.check(self.lib.sgmse_sb_sample(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, N, *[fp(v) for v in keep],
-                                                *[None if v is None else fp(v) for v in aff], int(bool(stochastic)), ptr(noise),
-                                                C.c_ulonglong(seed & (2 ** 64 - 1)), int(bool(use_graph)), C.byref(nfe)))
+            with self._windows_for_call(windows, window_batch):
+                self.check(self.lib.sgmse_sb_sample(self.h, Y.data_ptr(), out.data_ptr(), B, F_, T, N, *[fp(v) for v in keep],
+                                                    *[None if v is None else fp(v) for v in aff], int(bool(stochastic)), ptr(noise),
+                                                    C.c_ulonglong(seed & (2 ** 64 - 1)), int(bool(use_graph)), C.byref(nfe)))
             self._noise_frames_pending = False
 
         self._with_capturable_stream(run, use_graph)
@@ -675,6 +684,66 @@ class Context:
         arr = (_I * max(len(frames), 1))(*frames)
         self.check(self.lib.sgmse_set_frames(self.h, arr if frames else None, len(frames)))
         self._frames = frames
+
+    def set_windows(self, windows, window_batch=None) -> None:
+        """Window plan of the following pc_sample / sb_sample calls (sgmse_set_windows): ``windows`` = (W, starts), n windows of W
+        frames over a recording of K = starts[-1] + W frames, the network on chunks of up to ``window_batch`` (default: all n)
+        windows; None withdraws it.  Those calls then take ONE recording [1,1,F,K] and run one reverse process on it, only the
+        network windowed.  ValueError for a plan the library refuses.  (pc_sample / sb_sample set and withdraw their own
+        ``windows=`` argument; ode_sample refuses to run while a plan is in force.)"""
+        if windows is None:
+            if self._windows is not None:
+                self.check(self.lib.sgmse_set_windows(self.h, 0, 0, None, 0, 0))
+                self._windows = None
+            return
+        W, starts = windows
+        W, starts = int(W), [int(v) for v in starts]
+        if not starts:
+            raise ValueError("a window plan needs at least one start")
+        mb = len(starts) if window_batch is None else int(window_batch)
+        key = (W, tuple(starts), mb)
+        if key == self._windows:
+            return
+        self._windows = None
+        self.check(self.lib.sgmse_set_windows(self.h, starts[-1] + W, W, (_I * len(starts))(*starts), len(starts), mb))
+        self._windows = key
+
+    @contextlib.contextmanager
+    def _windows_for_call(self, windows, window_batch):
+        """The plan of one sampler call: set (None: whatever a set_windows call left is withdrawn) and withdrawn afterwards.  The
+        library keeps the last plan's captured step: the same plan in the next call does not capture again."""
+        self.set_windows(windows, window_batch)
+        try:
+            yield
+        finally:
+            self.set_windows(None)
+
+    def _uniform_window_op(self, fn, src, dst, F_: int, K: int, W: int, starts) -> None:
+        starts = [int(v) for v in starts]
+        if not starts:
+            raise ValueError("a window plan needs at least one start")
+        self.use_current_stream()
+        self.check(fn(self.h, src.data_ptr(), dst.data_ptr(), F_, K, int(W), (_I * len(starts))(*starts), len(starts)))
+
+    def window_gather(self, src: torch.Tensor, W: int, starts) -> torch.Tensor:
+        """sgmse_window_gather: src complex64 [F,K] -> windows complex64 [n,F,W], windows[j] = src[:, starts[j] : starts[j] + W]."""
+        src = check_tensor(src, "src", torch.complex64, self.device)
+        if src.dim() != 2:
+            raise ValueError(f"expected src of shape [F,K], got {tuple(src.shape)}")
+        F_, K = src.shape
+        out = torch.empty((len(starts), F_, int(W)), dtype=torch.complex64, device=self.device)
+        self._uniform_window_op(self.lib.sgmse_window_gather, src, out, F_, K, W, starts)
+        return out
+
+    def window_blend(self, windows: torch.Tensor, K: int, starts) -> torch.Tensor:
+        """sgmse_window_blend: windows complex64 [n,F,W] -> complex64 [F,K], the windows over a frame blended by their weights."""
+        windows = check_tensor(windows, "windows", torch.complex64, self.device)
+        if windows.dim() != 3 or windows.shape[0] != len(starts):
+            raise ValueError(f"expected windows of shape [{len(starts)},F,W], got {tuple(windows.shape)}")
+        _, F_, W = windows.shape
+        out = torch.empty((F_, int(K)), dtype=torch.complex64, device=self.device)
+        self._uniform_window_op(self.lib.sgmse_window_blend, windows, out, F_, int(K), W, starts)
+        return out
 
     def _window_call(self, fn, src, dst, F_: int, K: int, starts, frames, transform_type: int, factor: float, exponent: float) -> None:
         starts, frames = [int(v) for v in starts], [int(v) for v in frames]

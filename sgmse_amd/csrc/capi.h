@@ -212,6 +212,25 @@ int sgmse_spec_merge(sgmse_ctx* ctx, const void* windows, void* spec, int F, int
   return sg_guard(ctx, [&](sgmse::Engine& e) { e.op_spec_merge((const float2*)windows, (float2*)spec, F, K, start, frames, n, type, factor, exponent); });
 }
 
+int sgmse_window_gather(sgmse_ctx* ctx, const void* src, void* windows, int F, int K, int W, const int* start, int n) {
+  SG_ARG(ctx, src && windows && start && F > 0 && K > 0 && W > 0 && n > 0, "bad arguments");
+  const std::string bad = sgmse::Engine::window_plan_error(K, W, start, n);
+  SG_ARG(ctx, bad.empty(), bad);
+  return sg_guard(ctx, [&](sgmse::Engine& e) { e.op_window_gather((const float2*)src, (float2*)windows, F, K, W, start, n); });
+}
+
+int sgmse_window_blend(sgmse_ctx* ctx, const void* windows, void* dst, int F, int K, int W, const int* start, int n) {
+  SG_ARG(ctx, windows && dst && start && F > 0 && K > 0 && W > 0 && n > 0, "bad arguments");
+  const std::string bad = sgmse::Engine::window_plan_error(K, W, start, n);
+  SG_ARG(ctx, bad.empty(), bad);
+  return sg_guard(ctx, [&](sgmse::Engine& e) { e.op_window_blend((const float2*)windows, (float2*)dst, F, K, W, start, n); });
+}
+
+int sgmse_set_windows(sgmse_ctx* ctx, int K, int W, const int* start, int n, int max_batch) {
+  SG_ARG(ctx, n >= 0 && (n == 0 || start != nullptr), "bad window table");
+  return sg_guard(ctx, [&](sgmse::Engine& e) { e.set_windows(K, W, start, n, max_batch); });
+}
+
 int sgmse_upfirdn2d(sgmse_ctx* ctx, const float* input, const float* kernel, float* out, int BC, int H, int W, int kh, int kw,
                     int up_x, int up_y, int down_x, int down_y, int px0, int px1, int py0, int py1) {
   SG_ARG(ctx, input && kernel && out && BC > 0 && H > 0 && W > 0 && kh > 0 && kw > 0, "null pointer or non-positive shape");

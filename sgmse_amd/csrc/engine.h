@@ -400,9 +400,10 @@ class Engine {
   // (upload_tables), so one capture serves every utterance / batch of a run (the Python samplers draw a fresh seed per call)
   struct GraphKey {
     int B, F, T, corr, ncorr, pred, pf; const void* y; const void* noise; float theta; int dps;
+    int win = 0;      // serial number of the window plan the step evaluates the network under (set_windows), 0: none
     bool operator==(const GraphKey& o) const {
       return B == o.B && F == o.F && T == o.T && corr == o.corr && ncorr == o.ncorr && pred == o.pred && pf == o.pf && y == o.y &&
-             noise == o.noise && theta == o.theta && dps == o.dps;
+             noise == o.noise && theta == o.theta && dps == o.dps && win == o.win;
     }
   };
   // What the fixed-step samplers share in front of their loop.  fill(i, row) writes step i's row of the step table (row[SC_T] = its
@@ -456,7 +457,8 @@ class Engine {
     require_ready();
     SG_REQUIRE(sc.N >= 1 && sc.t && sc.dt && sc.G && sc.G2, "pc_sample: step table missing");
     SG_REQUIRE(sc.corrector != 1 || (sc.ald_eps && sc.ald_noise), "pc_sample: ALD table missing");
-    ensure_shape(B, F, T, sc.N);
+    if (windowed()) win_begin("pc_sample", B, F, T, sc.N);
+    else ensure_shape(B, F, T, sc.N);
     take_noise_frames("pc_sample", B, T, noise);
     SG_REQUIRE(!ragged() || sc.corrector != 2, "ragged batches: the Langevin corrector with the step size of the batch couples the utterances (correctors.py:50-52) "
                                                "and is not supported; corrector = 3 takes the step size per utterance");
@@ -483,12 +485,11 @@ class Engine {
     draw_prior(noise, st.seed, sc.std1, n, B, F * T);
     SG_CHECK(drt::memcpy_d2d(sxm_, sx_, n * 8, stream_));
     DRT_LAUNCH(step_set_kernel, dim3(1), dim3(64), stream_, step_ctr_.get(), 0);
+    if (windowed()) win_gather_y(F);
 
-    const long long FT = ragged() ? 1 : (long long)F * T;          // batch stride of x / y (ragged: multiplier of the utterance's offset)
     auto step_body = [&]() {
       for (int cs = 0; cs < ncorr; ++cs) {
-        arena_.reset();
-        run_forward(sx_, FT, sy_, FT, sscore_, B, F, T, ctl);
+        eval_score(B, F, T, ctl);
         SamplerArgs a = sa; a.draw_base = 1 + cs; a.draw_per_step = draws_per_step;
         if (sc.corrector == 3) {
           DRT_LAUNCH(sampler_langevin_norms_each_kernel, dim3(LANG_NBLK, B), dim3(256), stream_, a);
@@ -503,8 +504,7 @@ class Engine {
         }
       }
       if (sc.predictor == 1) {
-        arena_.reset();
-        run_forward(sx_, FT, sy_, FT, sscore_, B, F, T, ctl);
+        eval_score(B, F, T, ctl);
         SamplerArgs a = sa; a.draw_base = 1 + ncorr; a.draw_per_step = draws_per_step; a.add_noise = pred_noise ? 1 : 0;
         DRT_LAUNCH(sampler_revdiff_kernel, eg, dim3(256), stream_, a);
       }
@@ -513,7 +513,7 @@ class Engine {
       DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_.get());
     };
     run_steps(sc.N, GraphKey{B, F, T, sc.corrector, ncorr, sc.predictor, sc.probability_flow + (ctl.coef ? 2 : 0), (const void*)sy_, (const void*)noise,
-                             sc.theta + 1000.f * sc.snr * langevin, draws_per_step},      // (set_frames invalidates the graph itself)
+                             sc.theta + 1000.f * sc.snr * langevin, draws_per_step, win_key()},      // (set_frames invalidates the graph itself)
               sc.use_graph, step_body);
     SG_CHECK(drt::memcpy_d2d(out, sc.denoise ? sxm_ : sx_, n * 8, stream_));
     nfe_ = sc.N * (ncorr + 1);   // the reference counts N*(corrector.n_steps+1) whatever the predictor (sampling/__init__.py:67)
@@ -525,7 +525,8 @@ class Engine {
                  const float2* noise, unsigned long long seed, int use_graph) {
     require_ready();
     SG_REQUIRE(N >= 1 && t && w_prev && w_est && w_y && w_z, "sb_sample: step table missing");
-    ensure_shape(B, F, T, N);
+    if (windowed()) win_begin("sb_sample", B, F, T, N);
+    else ensure_shape(B, F, T, N);
     take_noise_frames("sb_sample", B, T, noise);
     const size_t n = ragged() ? rag_[0].pix : (size_t)B * F * T;     // complex elements of Y / the result, utterance after utterance
     const StepSetup st = begin_steps("sb_sample", Y, n, B, N, seed, [&](int i, float* r) {
@@ -540,14 +541,13 @@ class Engine {
     sa.table = step_table_; sa.step_ptr = step_ctr_; sa.n = (int)n; sa.add_noise = stochastic ? 1 : 0; sa.B = B; sa.per = F * T;
     sa.draw_base = 0; sa.draw_per_step = 1; sa.rag_off = rag_off0();
     const dim3 eg((unsigned)((n + 255) / 256));
-    const long long FT = ragged() ? 1 : (long long)F * T;          // batch stride of x / y (ragged: multiplier of the utterance's offset)
+    if (windowed()) win_gather_y(F);
     auto step_body = [&]() {
-      arena_.reset();
-      run_forward(sx_, FT, sy_, FT, sscore_, B, F, T, ctl);
+      eval_score(B, F, T, ctl);
       DRT_LAUNCH(sampler_sb_kernel, eg, dim3(256), stream_, sa);
       DRT_LAUNCH(step_inc_kernel, dim3(1), dim3(64), stream_, step_ctr_.get());
     };
-    run_steps(N, GraphKey{B, F, T, 100 + stochastic, 0, 0, ctl.coef ? 2 : 0, nullptr, (const void*)noise, 0.f, 1}, use_graph, step_body);
+    run_steps(N, GraphKey{B, F, T, 100 + stochastic, 0, 0, ctl.coef ? 2 : 0, nullptr, (const void*)noise, 0.f, 1, win_key()}, use_graph, step_body);
     SG_CHECK(drt::memcpy_d2d(out, sx_, n * 8, stream_));
     nfe_ = N;
   }
@@ -577,6 +577,7 @@ class Engine {
                unsigned long long seed, bool per_utterance) {
     require_ready();
     const std::string who = per_utterance ? "ode_sample_each" : "ode_sample";
+    if (windowed()) throw EngineArgError(who + ": a window plan (sgmse_set_windows) is not supported by the adaptive solver; withdraw it (n = 0)");
     SG_REQUIRE(per_utterance || !ragged(), "ode_sample: ragged batches are not supported: the solver's error norm couples the utterances of a batch "
                                            "(call sgmse_set_frames with n = 0 and pass a rectangular batch)");
     // (rtol, atol, first_step, max_step, max_nfe: checked once, at the C boundary)
@@ -786,6 +787,55 @@ class Engine {
     if (!bad.empty()) { geom_call_.clear(); streams_next_.clear(); throw EngineArgError(bad); }
   }
   void set_ragged_frames(const int* frames, int n) { set_frames(frames, n); }     // sgmse_set_frames
+
+  // ---- windowed score (sgmse_set_windows): ONE reverse process over a long recording, only the network runs on windows ------------
+  // With a plan in force pc_sample / sb_sample take B = 1, T = K and keep their state (sx_, sxm_, sy_, sscore_) at F * K elements,
+  // K any length; every score evaluation (eval_score) cuts the current state into the plan's n windows of W frames, runs the network
+  // on them in C = ceil(n / max_batch) chunks of Bc = ceil(n / C) windows and blends the windows' scores into the recording's
+  // (window_gather_kernel / window_blend_kernel).  The up to C - 1 empty slots of the last chunk evaluate its last window again
+  // (their scores are not blended), so the network runs at ONE shape and the whole step is one captured graph.  Sticky like
+  // set_frames; n = 0 withdraws the plan.  The plan's serial number is part of the captured step's key: the same plan given again
+  // (also after a withdrawal) keeps it.
+  static std::string window_plan_error(int K, int W, const int* start, int n) {
+    if (K < 1 || W < 1 || n < 1 || !start) return "a window plan needs K >= 1, W >= 1 and n >= 1 starts";
+    if (n > 32767) return "more than 32767 windows";      // (grid.z of the gather: up to C * Bc < 2 n slots)
+    for (int j = 0; j < n; ++j) {
+      if (start[j] < 0 || (long long)start[j] + W > K) return "window " + std::to_string(j) + " does not lie inside [0, K)";
+      if (j > 0 && start[j] <= start[j - 1]) return "window starts must be strictly increasing";
+      if (j == 0 ? start[0] != 0 : start[j] > start[j - 1] + W) return "the windows leave a gap: they must cover [0, K)";
+      if (j > 2 && start[j] < start[j - 3] + W) return "a frame lies under four windows";
+    }
+    if (start[n - 1] + W != K) return "the windows leave a gap: they must cover [0, K)";
+    return "";
+  }
+  void set_windows(int K, int W, const int* start, int n, int max_batch) {
+    if (n == 0) { win_on_ = false; return; }
+    const std::string bad = window_plan_error(K, W, start, n);
+    if (!bad.empty()) throw EngineArgError("set_windows: " + bad);
+    if (max_batch < 1) throw EngineArgError("set_windows: max_batch must be >= 1");
+    const int down = 1 << (cfg_.n_levels - 1);
+    if (W % down) throw EngineArgError("set_windows: W must be a multiple of 2^(levels-1) = " + std::to_string(down) + " (only the windows reach the network)");
+    WinPlan p;
+    p.K = K; p.W = W; p.n = n; p.max_batch = max_batch; p.start.assign(start, start + n);
+    p.C = (n + max_batch - 1) / max_batch; p.Bc = (n + p.C - 1) / p.C;
+    if (!p.same(win_)) { p.id = ++win_serial_; win_ = std::move(p); win_dirty_ = true; }
+    win_on_ = true;
+  }
+  bool windowed() const { return win_on_; }
+  // the two kernels on their own (sgmse_window_gather / sgmse_window_blend): the plan, checked by the caller, goes up through
+  // upload_windows, whose table begins with the n starts (the kernels read nothing behind them)
+  void op_window_gather(const float2* src, float2* windows, int F, int K, int W, const int* start, int n) {
+    SG_REQUIRE(F <= 65535, "window_gather: more than 65535 rows");
+    WinArgs a{src, windows, upload_windows(start, start, n), F, K, W, n};
+    DRT_LAUNCH(window_gather_kernel, dim3((W + 255) / 256, F, n), dim3(256), stream_, a);
+    check_launch();
+  }
+  void op_window_blend(const float2* windows, float2* dst, int F, int K, int W, const int* start, int n) {
+    SG_REQUIRE(F <= 65535, "window_blend: more than 65535 rows");
+    WinArgs a{windows, dst, upload_windows(start, start, n), F, K, W, n};
+    DRT_LAUNCH(window_blend_kernel, dim3((K + 255) / 256, F), dim3(256), stream_, a);
+    check_launch();
+  }
   int last_nfe() const { return nfe_; }
   int graph_captures() const { return graph_captures_; }     // how many times a step was captured + instantiated (tests, bench)
   int graph_updates() const { return graph_updates_; }       // ... captured and applied to the existing executable in place
@@ -1414,6 +1464,71 @@ class Engine {
       renew(coef_table_, rows * 16);
       temb_rows_ = (int)rows;
     }
+  }
+
+  // ---- windowed score (set_windows) ------------------------------------------------------------------------------
+  struct WinPlan {
+    int K = 0, W = 0, n = 0, max_batch = 0, C = 0, Bc = 0, id = 0; std::vector<int> start;
+    bool same(const WinPlan& o) const { return K == o.K && W == o.W && n == o.n && max_batch == o.max_batch && start == o.start; }
+  };
+  WinPlan win_; bool win_on_ = false, win_dirty_ = false; int win_serial_ = 0;
+  DevArray<int> win_plan_tab_;               // start[C * Bc]: the plan's starts, the last one repeated in the filler slots
+  DevArray<float2> win_x_, win_y_, win_score_;   // [Bc][F][W] gathered state of one chunk; [C * Bc][F][W] y and scores of all slots
+  int win_key() const { return win_on_ ? win_.id : 0; }
+  // A sampler call under the plan: what it refuses, the network's shape (Bc, F, W), state arrays of F * K elements, window buffers, the
+  // plan on the device.  A buffer that moved invalidates the captured step.
+  void win_begin(const std::string& who, int B, int F, int T, int nrows) {
+    const auto refuse = [&](const std::string& why) {
+      frames_next_.clear(); streams_next_.clear();      // (what was pending belonged to this call)
+      throw EngineArgError(who + ": " + why);
+    };
+    if (ragged()) refuse("a window plan (sgmse_set_windows) and a ragged batch (sgmse_set_frames) exclude each other");
+    if (!frames_next_.empty()) refuse("a window plan (sgmse_set_windows) draws the recording's own noise field: a noise geometry (sgmse_set_noise_frames) does not apply");
+    if (B != 1) refuse("a window plan (sgmse_set_windows) takes one recording: B must be 1, got " + std::to_string(B));
+    if (T != win_.K) refuse("T = " + std::to_string(T) + " is not the window plan's K = " + std::to_string(win_.K));
+    const int down = 1 << (cfg_.n_levels - 1);
+    if (win_.W % down) refuse("the window plan's W must be a multiple of 2^(levels-1) = " + std::to_string(down));
+    SG_REQUIRE(F <= 65535, "window plan: more than 65535 rows");
+    ensure_shape(win_.Bc, F, win_.W, nrows);
+    const size_t state = (size_t)F * win_.K * 8, slot = (size_t)F * win_.W * 8, slots = (size_t)win_.C * win_.Bc;
+    bool moved = false;
+    for (DevArray<float2>* q : {&sx_, &sxm_, &sscore_, &sy_}) moved |= grow(*q, state);
+    moved |= grow(win_x_, slot * win_.Bc);
+    moved |= grow(win_y_, slot * slots);
+    moved |= grow(win_score_, slot * slots);
+    moved |= grow(win_plan_tab_, slots * sizeof(int));
+    if (moved) invalidate_graph();
+    if (win_dirty_ || moved) {
+      int* h = reinterpret_cast<int*>(stage_.acquire(slots * sizeof(int)));
+      for (size_t j = 0; j < slots; ++j) h[j] = win_.start[std::min<size_t>(j, win_.n - 1)];
+      SG_CHECK(drt::memcpy_h2d(win_plan_tab_, h, slots * sizeof(int), stream_));
+      stage_.commit(stream_);
+      win_dirty_ = false;
+    }
+  }
+  void win_gather(const float2* src, float2* dst, int F, int first, int slots) {
+    WinArgs a{src, dst, win_plan_tab_.get() + first, F, win_.K, win_.W, slots};
+    DRT_LAUNCH(window_gather_kernel, dim3((win_.W + 255) / 256, F, slots), dim3(256), stream_, a);
+  }
+  void win_gather_y(int F) { win_gather(sy_, win_y_, F, 0, win_.C * win_.Bc); }      // once per sampler call
+  // One score evaluation of the samplers' step: sscore_ = network(sx_, sy_) of the batch, or, under a window plan, of the recording
+  // through its windows.
+  void eval_score(int B, int F, int T, const FwdCtl& ctl) {
+    if (!win_on_) {
+      const long long FT = ragged() ? 1 : (long long)F * T;          // batch stride of x / y (ragged: multiplier of the utterance's offset)
+      arena_.reset();
+      run_forward(sx_, FT, sy_, FT, sscore_, B, F, T, ctl);
+      return;
+    }
+    const long long FW = (long long)F * win_.W;
+    for (int c = 0; c < win_.C; ++c) {
+      const size_t off = (size_t)c * win_.Bc * FW;
+      win_gather(sx_, win_x_, F, c * win_.Bc, win_.Bc);
+      arena_.reset();
+      run_forward(win_x_, FW, win_y_ + off, FW, win_score_ + off, win_.Bc, F, win_.W, ctl);      // (the score wrapper reads the gathered x)
+    }
+    WinArgs a{win_score_, sscore_, win_plan_tab_, F, win_.K, win_.W, win_.n};
+    DRT_LAUNCH(window_blend_kernel, dim3((win_.K + 255) / 256, F), dim3(256), stream_, a);
   }
 
   void compute_temb(const float* t_dev, int rows) {

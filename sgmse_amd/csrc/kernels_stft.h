@@ -176,4 +176,60 @@ __global__ __launch_bounds__(256) void spec_merge_kernel(SpecWinArgs p) {
   p.dst[(size_t)f * p.K + k] = b;
 }
 
+// Windows of ONE width W over a recording [F][K] (sgmse_window_gather / sgmse_window_blend, the windowed score of
+// Engine::set_windows): window j holds the frames [start[j], start[j] + W) as block j of [n][F][W].  No transform.  The host has
+// checked the plan (window_plan_error): start[0] = 0, starts strictly increasing, no gap, start[n-1] + W = K, every frame under at
+// most three windows.
+struct WinArgs { const float2* src; float2* dst; const int* start; int F, K, W, n; };
+
+// grid = (ceil(W / 256), F, slots): win[j][f][t] = src[f][start[j] + t] for the `slots` table entries start[0 .. slots).  (The engine's
+// table repeats the last window in the filler slots of the last chunk.)
+__global__ __launch_bounds__(256) void window_gather_kernel(WinArgs p) {
+  const int t = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y, j = blockIdx.z;
+  if (t >= p.W) return;
+  p.dst[((size_t)j * p.F + f) * p.W + t] = p.src[(size_t)f * p.K + p.start[j] + t];
+}
+
+// weight of window j at its local frame t: 1 inside, rising over the overlap with window j - 1 (L_j frames), falling over the
+// overlap with window j + 1
+__device__ __forceinline__ float window_weight(const int* start, int n, int W, int j, int t) {
+  float w = 1.0f;
+  if (j > 0) w = fminf(w, ((float)t + 0.5f) / (float)(start[j - 1] + W - start[j]));
+  if (j < n - 1) w = fminf(w, ((float)(W - t) - 0.5f) / (float)(start[j] + W - start[j + 1]));
+  return w;
+}
+
+// grid = (ceil(K / 256), F): one thread per output element (f, k), no atomics.  The windows over frame k are j0, the first whose end
+// lies behind k (binary search: ends increase), and up to two successors that start at or before k.  With a the first one's value and
+// S the sum of the weights (ascending j): out = a, then out = fmaf(w_j / S, v_j - a, out) for each later one -- a frame under one
+// window is that window's value bit for bit, windows that agree give their common value bit for bit.
+__global__ __launch_bounds__(256) void window_blend_kernel(WinArgs p) {
+  const int k = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
+  if (k >= p.K) return;
+  const int* start = p.start;
+  int lo = 0, hi = p.n - 1;                  // start[n-1] + W = K > k
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (start[mid] + p.W > k) hi = mid; else lo = mid + 1;
+  }
+  const int j0 = lo;
+  float w[3];
+  float2 v[3];
+  int m = 0;
+  float S = 0.f;
+  for (int j = j0; j < p.n && m < 3 && start[j] <= k; ++j, ++m) {
+    const int t = k - start[j];
+    w[m] = window_weight(start, p.n, p.W, j, t);
+    v[m] = p.src[((size_t)j * p.F + f) * p.W + t];
+    S += w[m];
+  }
+  float2 out = v[0];
+  for (int i = 1; i < m; ++i) {
+    const float r = w[i] / S;
+    out.x = fmaf(r, v[i].x - v[0].x, out.x);
+    out.y = fmaf(r, v[i].y - v[0].y, out.y);
+  }
+  p.dst[(size_t)f * p.K + k] = out;
+}
+
 }  // namespace sgmse

@@ -26,6 +26,8 @@ Differences from the reference script, none of them in the arithmetic of one utt
   REFERENCE, which has no such mode and enhances every recording as one spectrogram: a windowed file is not what the reference
   computes for it.  Files of at most W frames stay in the batches above, unchanged.  ``--window_noise recording`` gives the
   windows of a file one noise field, indexed by the file's frame, instead of one unrelated field per window;
+  ``--window_blend score`` runs ONE reverse process over such a file and windows only the network (all windows W frames, their
+  scores blended at every evaluation, ``ScoreModel.enhance_long(window_blend="score")``);
 * audio I/O uses ``soundfile`` when it is installed; otherwise ``scipy.io.wavfile`` for wav and the package's own decoder
   (util/flac.py) for flac input; resampling to the
   model's rate uses ``scipy.signal.resample_poly`` (the reference: ``librosa.resample``).
@@ -302,7 +304,8 @@ def enhance_long_files(model: ScoreModel, files: List[str], test_dir: str, enhan
     for path, g in zip(files, gidx):
         y = torch.from_numpy(_load_wave(path, target_sr))
         x, _ = model.enhance_long(y, window_frames=args.window_frames, overlap_frames=args.window_overlap, batch_size=args.batch_size,
-                                  seed=args.seed, stream=g, window_noise=getattr(args, "window_noise", None) or "window", **kw)
+                                  seed=args.seed, stream=g, window_noise=getattr(args, "window_noise", None) or "window",
+                                  window_blend=getattr(args, "window_blend", None) or "output", **kw)
         name = path.replace(test_dir, "")
         name = name[1:] if name.startswith("/") else name
         write_audio(join(enhanced_dir, name), x.cpu().numpy(), target_sr)
@@ -494,6 +497,11 @@ def main(argv=None) -> int:
                         help="With --window_frames: 'window' (the default) = every window draws its own noise, so the frames two windows "
                              "share are cross-faded between two independent samples; 'recording' = one noise field per file, indexed by the "
                              "file's frame, which the windows over a frame share")
+    parser.add_argument("--window_blend", type=str, choices=("output", "score"), default=None,
+                        help="With --window_frames: 'output' (the default) = every window is its own reverse process and the enhanced "
+                             "windows are cross-faded; 'score' = ONE reverse process over the whole file, only the network runs on windows "
+                             "(all of W frames, --batch_size at a time) and their scores are blended at every evaluation: no seams, one noise "
+                             "field (--window_noise is not consulted), not with the adaptive ODE solver")
     parser.add_argument("--balance", type=str, choices=("contiguous", "frames"), default="contiguous",
                         help="Files per rank under torchrun: the reference's contiguous split of the sorted list (default), or balanced by "
                              "padded frame count (longest-processing-time); the enhanced files are identical either way")
@@ -501,6 +509,8 @@ def main(argv=None) -> int:
     args = parser.parse_args(argv)
     if args.window_noise is not None and args.window_frames <= 0:
         raise ValueError("--window_noise applies to windowed enhancement: pass --window_frames")
+    if args.window_blend is not None and args.window_frames <= 0:
+        raise ValueError("--window_blend applies to windowed enhancement: pass --window_frames")
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     device = torch.device(args.device)

@@ -346,12 +346,13 @@ class ScoreModel(nn.Module):
         return wave, nfe, (time.time() - t_begin) / (len(wave) / self.sr)
 
     def _batch_sampler(self, Y, N, corrector, corrector_steps, snr, noise, seed, predictor, sampler_type, use_graph, streams, corrector_scope,
-                       ode_kwargs, noise_frames=None, minibatch=None):
+                       ode_kwargs, noise_frames=None, minibatch=None, windows=None, window_batch=None):
         """The zero-argument sampler of ``enhance_batch`` / ``enhance_long`` for spectrograms Y (a tensor [B,1,F,T] or a ragged list)."""
         sb = type(self.sde).__name__ == "SBVESDE"
         if ode_kwargs and (sb or sampler_type != "ode"):
             raise TypeError(f"unexpected keyword arguments {sorted(ode_kwargs)} (get_ode_sampler's apply with sampler_type='ode' on an OUVE model)")
-        extra = {k: v for k, v in (("noise_frames", noise_frames), ("minibatch", minibatch)) if v is not None}
+        extra = {k: v for k, v in (("noise_frames", noise_frames), ("minibatch", minibatch), ("windows", windows),
+                                   ("window_batch", window_batch if windows is not None else None)) if v is not None}
         if sb:
             return self.get_sb_sampler(sde=self.sde, y=Y, sampler_type="ode" if sampler_type == "pc" else sampler_type, noise=noise, seed=seed,
                                        use_graph=use_graph, streams=streams, **extra)
@@ -396,6 +397,25 @@ class ScoreModel(nn.Module):
         return x_hat, nfe
 
     # -- long recordings: windows with cross-faded overlaps (not in the reference) ------------------------------------------------
+    def _enhance_long_score(self, y, K, starts, W, batch_size, seed, stream, return_windows, sampler_args):
+        """``enhance_long(window_blend="score")`` of a recording y [1,L] (on the device) of K frames and more than one window."""
+        args = dict(N=30, corrector="ald", corrector_steps=1, snr=0.5, noise=None, predictor="reverse_diffusion", sampler_type="pc",
+                    use_graph=True, corrector_scope="batch")
+        ode_kwargs = {k: v for k, v in sampler_args.items() if k not in args and k != "pad_mode"}
+        args.update({k: v for k, v in sampler_args.items() if k in args})
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        L = y.size(1)
+        peak = float(y.abs().max()) or 1.0
+        # (the division by a tensor on the device: what enhance_batch does, see enhance_long)
+        Y = self._forward_transform(self._stft(y / y.new_tensor(peak))).unsqueeze(1)       # [1,1,F,K]
+        sample, nfe = self._batch_sampler(Y, seed=seed, streams=[stream], ode_kwargs=ode_kwargs, windows=(W, starts),
+                                          window_batch=max(int(batch_size), 1), **args)()
+        info = dict(starts=starts, frames=[W] * len(starts), nfe=[nfe])
+        if return_windows:
+            info["windows"] = None
+        return self.to_audio(sample[:, 0], L)[0] * peak, info
+
     def _batch_coupling(self, sampler_type="pc", corrector="ald", corrector_scope="batch", adaptive=None, denoise=True, solver="scipy",
                         step_control="batch", **_):
         """Why this sampler configuration makes an utterance depend on what shares its batch (and what to use instead), or None."""
@@ -414,7 +434,7 @@ class ScoreModel(nn.Module):
         return None
 
     def enhance_long(self, y, window_frames=512, overlap_frames=64, batch_size=32, seed=None, stream=0, return_windows=False,
-                     window_noise="window", **sampler_args):
+                     window_noise="window", window_blend="output", **sampler_args):
         """Enhancement of a recording of any length in windows of at most ``window_frames`` spectrogram frames whose neighbours
         overlap by ``overlap_frames`` (up to 63 more for the last one) and are cross-faded: memory is bounded by ``batch_size``
         windows instead of growing with the recording, and the network sees the context length it was trained on.  Not in the
@@ -441,12 +461,26 @@ class ScoreModel(nn.Module):
         A recording of ONE window (K <= window_frames) takes the existing path, bit for bit: ``enhance_batch([y], streams=[stream])``
         with pad_spec and ``pad_mode`` (a coupling configuration: the tensor form ``enhance_batch(y[None])``, which takes it).
 
+        ``window_blend``: 'output' (default) -- the above: every window its own reverse process, the enhanced windows cross-faded;
+        'score' -- ONE reverse process over the whole recording, only the network windowed: one peak, one STFT, spec_fwd of the whole
+        spectrogram, ONE sampler call on [1,1,F,K] under the uniform plan (util/windows.plan_windows_uniform: all windows
+        ``window_frames`` frames, the last pulled left) with ``window_batch=batch_size`` (Context.set_windows: every score evaluation
+        gathers the state's windows, runs the network on up to ``batch_size`` of them at a time and blends their scores), spec_back,
+        iSTFT, times the peak.  There are no seams to cross-fade; state and sampler updates cost 4 * 8 F K bytes, the network's memory
+        is still bounded by ``batch_size`` windows; the result does not depend on ``batch_size``.  The noise is the recording's own
+        field, drawn from (seed, ``stream``) at the recording's index: ``window_noise`` is NOT consulted in this mode.  'langevin' at
+        batch scope runs (the "batch" is the recording); the adaptive ODE solver raises ValueError; replayed ``noise`` is the
+        recording's, [ndraws,1,1,F,K].  info['frames'] is then [window_frames] * n and info['nfe'] the one call's count; with
+        ``return_windows`` info['windows'] is None (there are none).  Any other value raises ValueError.
+
         Returns (waveform float32 [L] on the model's device, info): info['starts'], info['frames'] the plan, info['nfe'] the list of
         the sampler calls' evaluation counts; with ``return_windows`` info['windows'], the enhanced windows [F,T_i] in the
         transformed domain (None for a one-window recording, whose spectrogram the existing path does not return)."""
-        from .util.windows import WINDOW_NOISE, plan_windows, window_noise_plan
+        from .util.windows import WINDOW_NOISE, plan_windows, plan_windows_uniform, window_noise_plan
         if window_noise not in WINDOW_NOISE:
             raise ValueError(f"window_noise must be 'window' or 'recording', got {window_noise!r}")
+        if window_blend not in ("output", "score"):
+            raise ValueError(f"window_blend must be 'output' or 'score', got {window_blend!r}")
         dev = self._device()
         y = y.reshape(1, -1).to(dev)
         L = y.size(1)
@@ -464,6 +498,9 @@ class ScoreModel(nn.Module):
             if return_windows:
                 info["windows"] = None
             return xs[0], info
+        if window_blend == "score":
+            return self._enhance_long_score(y, K, plan_windows_uniform(K, window_frames, overlap_frames), int(window_frames), batch_size,
+                                            seed, stream, return_windows, sampler_args)
         if coupling is not None:
             raise ValueError(f"enhance_long: a recording of {len(starts)} windows would depend on batch_size: {coupling}")
         if sampler_args.get("noise") is not None:

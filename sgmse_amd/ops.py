@@ -187,6 +187,20 @@ def spec_split(spec: torch.Tensor, starts, frames, transform_type: str, factor: 
     return [w[0] for w in _lib._unpack_ragged(packed, [int(v) for v in frames], int(spec.shape[0]))]
 
 
+def window_gather(src: torch.Tensor, W: int, starts) -> torch.Tensor:
+    """The windows [:, starts[j] : starts[j] + W] of src complex64 [F,K] as one complex64 [n,F,W] tensor: a plain copy
+    (sgmse_window_gather).  The plan (util/windows.plan_windows_uniform, or any other that covers [0, K) with windows of W frames
+    and at most three per frame) is checked by the library."""
+    return default_context(src.device).window_gather(src, W, starts)
+
+
+def window_blend(windows: torch.Tensor, K: int, starts) -> torch.Tensor:
+    """complex64 [F,K] from the windows complex64 [n,F,W] over the frames [starts[j], starts[j] + W): a frame under one window is that
+    window's element, a frame under two or three their blend by weights that rise and fall linearly over the overlaps
+    (sgmse_window_blend); no spectrogram transform."""
+    return default_context(windows.device).window_blend(windows, K, starts)
+
+
 def spec_merge(windows, starts, frames, K: int, transform_type: str, factor: float, exponent: float) -> torch.Tensor:
     """spec_back of the windows (a list of [F,T_i] or [1,F,T_i] tensors in the transformed domain, or their packed buffer) joined to
     complex64 [F,K]: a frame under one window is ``spec_transform(..., inverse=True)`` of it, a frame under two is the linear

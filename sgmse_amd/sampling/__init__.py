@@ -50,10 +50,21 @@ def _require_native_for_noise_frames(ctx, noise_frames):
                          "the Python loop, which draws from torch's generator")
 
 
+def _require_native_for_windows(ctx, windows):
+    """A window plan (Context.set_windows) is the library loops' windowed score evaluation."""
+    if ctx is None and windows is not None:
+        raise ValueError("windows applies to the native HIP samplers (one reverse process over the recording, the network on windows); "
+                         "this configuration runs the Python loop")
+
+
+def _window_kwargs(windows, window_batch):
+    return {} if windows is None else dict(windows=windows, window_batch=window_batch)
+
+
 def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=True, eps=3e-2, snr=0.1, corrector_steps=1,
                    probability_flow: bool = False, intermediate=False, noise: Optional[torch.Tensor] = None,
                    seed: Optional[int] = None, use_graph: bool = True, force_python_loop: bool = False, streams=None,
-                   corrector_scope: str = "batch", noise_frames=None, **kwargs):
+                   corrector_scope: str = "batch", noise_frames=None, windows=None, window_batch=None, **kwargs):
     """Predictor-corrector sampler (reference sampling/__init__.py:26-70).
 
     Extra keyword arguments of this implementation: ``noise`` (complex64 [ndraws,B,1,F,T] replayed standard-normal
@@ -65,7 +76,11 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=Tru
     loop gives it and ``y`` may be a ragged list; accepted with every corrector, it only matters for 'langevin').  With a ragged
     list ``y``, ``noise`` is a list of [ndraws,1,F,T_b] tensors.  ``noise_frames``: one (first_frame, total_frames) per utterance --
     the utterance is that stretch of a recording of total_frames frames and draws the noise those frames draw (Context.set_noise_frames),
-    so windows of one recording that share a stream id carry ONE noise field; default: an utterance is its own recording."""
+    so windows of one recording that share a stream id carry ONE noise field; default: an utterance is its own recording.
+    ``windows`` = (W, starts) (util/windows.plan_windows_uniform), ``window_batch``: ``y`` is ONE recording [1,1,F,K] of any length
+    K = starts[-1] + W and the sampler runs one reverse process on it -- state, noise and updates are the recording's -- with only
+    the network evaluated on the windows, up to ``window_batch`` at a time, and their scores blended (Context.set_windows).  Library
+    loop only: a configuration that runs the Python loop raises ValueError."""
     if corrector_scope not in ("batch", "utterance"):
         raise ValueError(f"corrector_scope must be 'batch' or 'utterance', got {corrector_scope!r}")
     predictor_cls = PredictorRegistry.get_by_name(predictor_name)   # ValueError for unknown names, like the reference
@@ -76,6 +91,7 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=Tru
     ctx = _native_engine(score_fn, y) if native else None
     _require_native_for_ragged(ctx, y)
     _require_native_for_noise_frames(ctx, noise_frames)
+    _require_native_for_windows(ctx, windows)
 
     if ctx is not None:
         table = sde.step_table(eps, snr, sde.N)
@@ -89,7 +105,7 @@ def get_pc_sampler(predictor_name, corrector_name, sde, score_fn, y, denoise=Tru
                                          corrector_steps=corrector_steps, predictor=predictor_name,
                                          probability_flow=False, denoise=denoise, noise=noise, seed=s, use_graph=use_graph,
                                          affine=affine, snr=snr, streams=streams, corrector_scope=corrector_scope,
-                                         noise_frames=noise_frames)
+                                         noise_frames=noise_frames, **_window_kwargs(windows, window_batch))
             return out, nfe
         return native_pc_sampler
 
@@ -228,7 +244,7 @@ def _native_ode_sampler(sde, score_fn, y, inverse_scaler, denoise, rtol, atol, m
 def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e-5, atol=1e-5, method="RK45", eps=3e-2,
                     device=None, noise: Optional[torch.Tensor] = None, seed: Optional[int] = None, use_graph: bool = True,
                     streams=None, adaptive: Optional[bool] = None, solver: str = "scipy", step_control: str = "batch", noise_frames=None,
-                    **kwargs):
+                    windows=None, window_batch=None, **kwargs):
     """Probability-flow sampler (reference sampling/__init__.py:73-143), in two forms.
 
     ``adaptive=True`` -- the reference's own behaviour: scipy's black-box solver (``method``, ``rtol``, ``atol``, extra keyword
@@ -247,7 +263,10 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
 
     ``adaptive=None`` (default) follows the reference where the reference runs: its function only completes with
     ``denoise=False`` (with the default ``denoise=True`` it raises TypeError), so ``denoise=False`` selects
-    the adaptive solver and the default selects the fixed-step sampler."""
+    the adaptive solver and the default selects the fixed-step sampler.
+
+    ``windows``, ``window_batch`` (see get_pc_sampler): the fixed-step sampler in the library only; the adaptive solver raises
+    ValueError (its error norm and step control are not built for a windowed score)."""
     if solver not in ("scipy", "native"):
         raise ValueError(f"solver must be 'scipy' or 'native', got {solver!r}")
     if step_control not in ("batch", "utterance"):
@@ -257,6 +276,9 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
                          "flattened batch under one error norm)")
     if adaptive is None:
         adaptive = denoise is False
+    if windows is not None and (adaptive or solver == "native"):
+        raise ValueError("windows is not supported by the adaptive ODE sampler (scipy or native): use the fixed-step sampler "
+                         "(adaptive=False), get_pc_sampler or get_sb_sampler")
     if solver == "native":
         if not adaptive:
             raise ValueError("solver='native' selects the adaptive solver's implementation: pass adaptive=True (or denoise=False); the fixed-step "
@@ -279,6 +301,7 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
     ctx = _native_engine(score_fn, y) if isinstance(sde, OUVESDE) else None
     _require_native_for_ragged(ctx, y)
     _require_native_for_noise_frames(ctx, noise_frames)
+    _require_native_for_windows(ctx, windows)
     if ctx is None:
         rsde = sde.reverse(score_fn, probability_flow=True)
 
@@ -302,24 +325,26 @@ def get_ode_sampler(sde, score_fn, y, inverse_scaler=None, denoise=True, rtol=1e
         with torch.no_grad():
             return ctx.pc_sample(y, table, theta=float(sde.theta), std1=std1, corrector="none", corrector_steps=1,
                                  predictor="reverse_diffusion", probability_flow=True, denoise=False, noise=noise, seed=s,
-                                 use_graph=use_graph, affine=affine, streams=streams, noise_frames=noise_frames)
+                                 use_graph=use_graph, affine=affine, streams=streams, noise_frames=noise_frames,
+                                 **_window_kwargs(windows, window_batch))
     return ode_sampler
 
 
 def get_sb_sampler(sde, model, y, eps=1e-4, n_steps=50, sampler_type="ode", noise: Optional[torch.Tensor] = None,
                    seed: Optional[int] = None, use_graph: bool = True, force_python_loop: bool = False, streams=None, noise_frames=None,
-                   **kwargs):
+                   windows=None, window_batch=None, **kwargs):
     """Schroedinger-bridge samplers (reference sampling/__init__.py:145-249): 'ode' (deterministic) and 'sde'.  With a
     ScoreModel on a HIP backbone the N-step loop runs in the library (sgmse_sb_sample); otherwise the reference-style
     Python loop below.  Returns a zero-argument callable -> (sample, n_steps) like the reference.  The library loop also takes a
     ragged list of [F,T_b] / [1,F,T_b] spectrograms (and then ``noise`` as a list of [ndraws,1,F,T_b]) and returns a list of
     [1,F,T_b], every utterance bit-identical to its own single-utterance call; the Python loop refuses a list.  ``noise_frames``
-    (library loop, 'sde'): see get_pc_sampler."""
+    (library loop, 'sde'): see get_pc_sampler.  ``windows``, ``window_batch`` (library loop): see get_pc_sampler."""
     if sampler_type not in ("ode", "sde"):
         raise ValueError("Invalid type. Choose 'ode' or 'sde'.")
     ctx = None if force_python_loop else (_native_engine(model, y) if isinstance(sde, SBVESDE) else None)
     _require_native_for_ragged(ctx, y)
     _require_native_for_noise_frames(ctx, noise_frames)
+    _require_native_for_windows(ctx, windows)
     if ctx is not None:
         table = sde.sb_step_table(eps, sampler_type, sde.N)
         affine = model.score_affine(table["t"])
@@ -329,7 +354,8 @@ def get_sb_sampler(sde, model, y, eps=1e-4, n_steps=50, sampler_type="ode", nois
             with torch.no_grad():
                 y0 = list(y) if isinstance(y, (list, tuple)) else y[:, [0], :, :].contiguous()
                 out, _ = ctx.sb_sample(y0, table, stochastic=(sampler_type == "sde"), noise=noise, seed=s,
-                                       affine=affine, use_graph=use_graph, streams=streams, noise_frames=noise_frames)
+                                       affine=affine, use_graph=use_graph, streams=streams, noise_frames=noise_frames,
+                                       **_window_kwargs(windows, window_batch))
             return out, n_steps
         return native_sb_sampler
 

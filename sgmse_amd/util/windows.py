@@ -35,6 +35,24 @@ def plan_windows(K: int, window_frames: int, overlap_frames: int) -> Tuple[List[
     return [j * P for j in range(n - 1)] + [K - T_last], [W] * (n - 1) + [T_last]
 
 
+def plan_windows_uniform(K: int, window_frames: int, overlap_frames: int) -> List[int]:
+    """Starts of the windows of ``enhance_long(window_blend="score")`` over K frames: ALL of exactly W = window_frames frames
+    (the network runs at one shape), W = window_frames, O = overlap_frames, P = W - O; the argument checks of ``plan_windows``.
+
+    K <= W: [0] -- one window; the caller takes the ordinary path, as with ``plan_windows``.
+    K > W:  n = ceil((K - O) / P) windows (``plan_windows``' count); window j < n - 1 starts at j P, the last one at K - W: pulled
+            left, never padded.  K - (n - 1) P lies in (O, W], so the starts strictly increase and the last overlap is at least O.
+            The last window starts inside the overlap of windows n - 3 and n - 2 when K - (n - 1) P < 2 O: a frame may lie under
+            THREE windows (never four: K - W > (n - 2) P >= (n - 4) P + W, as W >= 2 O), which sgmse_window_blend handles."""
+    K, W, O = int(K), int(window_frames), int(overlap_frames)
+    plan_windows(K, W, O)                                     # (the argument checks)
+    if K <= W:
+        return [0]
+    P = W - O
+    n = -(-(K - O) // P)
+    return [j * P for j in range(n - 1)] + [K - W]
+
+
 def window_stream(stream: int, i: int) -> int:
     """Noise-stream id of window i of the recording whose own id is ``stream``: window 0 keeps the recording's id, so a recording
     of one window draws the noise it draws without windows; the window index goes into the id's high word."""

@@ -3,9 +3,12 @@
 ScoreModel.enhance_long (random-init full-width ncsnpp, PC N=30, W = 512 frames, O = 64, 32 windows per sampler call) on one GPU,
 next to the same process's plain batch-32 x 4 s step (the tools/dir_job_bench.py pattern).  Reports seconds of audio per second for
 both, their ratio (arithmetic alone says 1 / (W / (W - O)) = 0.875) and the activation arena.  Every GPU step runs under its own
-time limit: when one runs out the process ends there and starts nothing more.  Prints one JSON object.
+time limit: when one runs out the process ends there and starts nothing more.  Prints one JSON object per ``--window_blend`` mode
+('output': every window its own reverse process, cross-faded; 'score': one reverse process, the network windowed); several modes
+run one after the other in the one process, next to the one plain step.
 
-    python tools/long_recording_bench.py [--minutes 10] [--window_frames 512] [--window_overlap 64] [--batch 32] [--N 30] [--out FILE]
+    python tools/long_recording_bench.py [--minutes 10] [--window_frames 512] [--window_overlap 64] [--batch 32] [--N 30]
+                                         [--window_blend output [score]] [--out FILE]
 """
 import argparse
 import contextlib
@@ -39,6 +42,7 @@ def main():
     ap.add_argument("--window_overlap", type=int, default=64)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--N", type=int, default=30)
+    ap.add_argument("--window_blend", type=str, nargs="+", choices=("output", "score"), default=["output"])
     ap.add_argument("--out", type=str, default=None)
     a = ap.parse_args()
     import torch
@@ -69,33 +73,37 @@ def main():
 
     L = int(a.minutes * 60 * 16000)
     rec = 0.1 * torch.randn(L, generator=torch.Generator().manual_seed(2))
-    win = dict(window_frames=a.window_frames, overlap_frames=a.window_overlap, batch_size=a.batch)
-    with limit(120, "windowed warm-up"):          # one sampler call's worth of windows
-        warm = min(L, (a.batch * (a.window_frames - a.window_overlap) + a.window_overlap - 1) * 128)
-        model.enhance_long(rec[:warm], seed=3, **win, **kw)
-        sync()
-    with limit(600, "windowed run"):
-        t0 = time.perf_counter()
-        x, info = model.enhance_long(rec, seed=4, **win, **kw)
-        sync()
-        long_s = time.perf_counter() - t0
-    ok = bool(torch.isfinite(x).all()) and x.shape == (L,)
-    plain_rate = a.batch * 4.0 / plain_s
-    long_rate = (L / 16000) / long_s
     P = a.window_frames - a.window_overlap
-    res = {"minutes": a.minutes, "frames": L // 128 + 1, "windows": len(info["starts"]), "last_window_frames": info["frames"][-1],
-           "sampler_calls": len(info["nfe"]), "window_frames": a.window_frames, "window_overlap": a.window_overlap, "batch": a.batch,
-           "N": a.N, "finite": ok, "wall_s_windowed": long_s, "audio_s_per_s_windowed": long_rate,
-           "wall_s_plain_step": plain_s, "audio_s_per_s_plain_step_same_process": plain_rate,
-           "windowed_over_plain": long_rate / plain_rate, "expected_from_arithmetic": P / a.window_frames,
-           "arena_bytes_plain_step": arena_plain, "arena_bytes_windowed": eng.arena_bytes(),
-           "graph_captures": eng.graph_captures(), "graph_updates": eng.graph_updates()}
-    line = json.dumps(res)
-    print(line)
+    lines = []
+    for mode in a.window_blend:
+        win = dict(window_frames=a.window_frames, overlap_frames=a.window_overlap, batch_size=a.batch, window_blend=mode)
+        with limit(120, f"windowed warm-up ({mode})"):          # one sampler call's worth of windows
+            warm = min(L, (a.batch * P + a.window_overlap - 1) * 128)
+            model.enhance_long(rec[:warm], seed=3, **win, **kw)
+            sync()
+        captures = eng.graph_captures()
+        with limit(600, f"windowed run ({mode})"):
+            t0 = time.perf_counter()
+            x, info = model.enhance_long(rec, seed=4, **win, **kw)
+            sync()
+            long_s = time.perf_counter() - t0
+        ok = bool(torch.isfinite(x).all()) and x.shape == (L,)
+        plain_rate = a.batch * 4.0 / plain_s
+        long_rate = (L / 16000) / long_s
+        res = {"window_blend": mode, "minutes": a.minutes, "frames": L // 128 + 1, "windows": len(info["starts"]),
+               "last_window_frames": info["frames"][-1],
+               "sampler_calls": len(info["nfe"]), "window_frames": a.window_frames, "window_overlap": a.window_overlap, "batch": a.batch,
+               "N": a.N, "finite": ok, "wall_s_windowed": long_s, "audio_s_per_s_windowed": long_rate,
+               "wall_s_plain_step": plain_s, "audio_s_per_s_plain_step_same_process": plain_rate,
+               "windowed_over_plain": long_rate / plain_rate, "expected_from_arithmetic": P / a.window_frames,
+               "arena_bytes_plain_step": arena_plain, "arena_bytes_windowed": eng.arena_bytes(),
+               "graph_captures": eng.graph_captures(), "graph_captures_timed_run": eng.graph_captures() - captures,
+               "graph_updates": eng.graph_updates()}
+        lines.append(json.dumps(res))
+        print(lines[-1], flush=True)
     if a.out:
         with open(a.out, "w") as f:
-            f.write(line + "\n")
-
+            f.write("\n".join(lines) + "\n")
 
 if __name__ == "__main__":
     main()
